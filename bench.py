@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py - 4-step iCD images/sec on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--arch sd15|sdxl] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--arch sd15|sdxl] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: set-up, W warm-up steps, EXACTLY K timed steps of the primary leg, the outputs of the last
+timed step under DIR (--dump-outputs) and the JSON line.  Everything else described below (the other BASELINE configurations, the
+roofline / event passes, the CPU baseline, the VAE leg, the other precisions, the live counter passes) runs with --full only.
 
 A "step" = one pass of the hot path over one batch of synthetic latents: the Generator.cons_generation loop
 (4 U-Net evaluations at the released timesteps + 4 boundary steps) on the configuration BASELINE.json's metric is quoted
@@ -12,7 +16,7 @@ the timed region (`--gather images`: per-rank VAE decode + uint8 images instead)
 outside this path and not part of `value` by default.  `python bench.py --gpus N` without a
 launcher re-executes itself under torch.distributed.run with N ranks (rendezvous on a free port of 127.0.0.1).
 
-The default run (no --arch/--batch) carries every BASELINE configuration's per-GPU share on the same JSON line:
+The --full run without --arch/--batch carries every BASELINE configuration's per-GPU share on the same JSON line:
   value / config      configs[1]  SD1.5 4-step reverse, 32 images per GPU
   "edit"              configs[2]  SD1.5 4-step inversion + 4-step reverse with p2p.AttentionStore, 8 images per GPU
   "sdxl"              configs[3]  SDXL 4-step reverse, 8 images per GPU (64 over 8 GPUs)
@@ -40,11 +44,17 @@ PEAK_HBM = 8.0e12
 ALGO_TFLOP_PER_SAMPLE_FWD = {"sd15": 0.8033, "sdxl": 6.7612}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline `value`: the other BASELINE configurations, roofline / event "
+                         "passes, precision comparisons, the VAE leg, live counter passes and the CPU baseline (off: a plain run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the primary leg's last timed step returned as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all; a fixed, seeded sample of larger outputs)")
     ap.add_argument("--arch", default="sd15", choices=["sd15", "sdxl"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default 32 for sd15, 8 for sdxl)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -93,7 +103,28 @@ def parse():
     ap.add_argument("--attn-valu-scale", type=int, default=0, choices=[0, 1],
                     help="A/B switch (UNet option attn_valu_scale): 1 = flash attention applies the softmax offset with an FMA per score "
                          "on the VALU, 0 (default) = the MFMA subtracts it")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: {name: tensor or array} -> dirname/<name>.npy in float32 (float64 stays float64).  Over `limit` bytes in all, each array is
+    cut to its share of the limit by a fixed, seeded sample of its flattened elements (sorted indices, the same on every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, x in arrays.items():
+        x = torch.as_tensor(x).detach().cpu()
+        x = (x.double() if x.dtype == torch.float64 else x.float()).numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), x)
 
 
 def free_port():
@@ -299,8 +330,8 @@ def live_traffic(arch, batch, family, timeout_s=240, leg="all"):
         if k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "GROUP_RANK", "ROLE_RANK", "ROLE_NAME", "LOCAL_WORLD_SIZE",
                  "GROUP_WORLD_SIZE", "ROLE_WORLD_SIZE", "TORCH_NCCL_ASYNC_ERROR_HANDLING") or k.startswith("TORCHELASTIC_"):
             env.pop(k)
-    child = [sys.executable, os.path.abspath(__file__), "--arch", arch, "--batch", str(batch), "--steps", "1", "--warmup", "1", "--in-flight", "1",
-             "--no-cpu-baseline", "--no-vae", "--no-ref-batching", "--no-profile", "--no-sdxl", "--no-live-traffic"]
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--arch", arch, "--batch", str(batch), "--steps", "1", "--warmup", "1",
+             "--in-flight", "1", "--no-cpu-baseline", "--no-vae", "--no-ref-batching", "--no-profile", "--no-sdxl", "--no-live-traffic"]
     child += ["--leg", "edit", "--in-flight-edit", "1"] if leg == "edit" else ["--no-edit"]
     try:
         per = {}
@@ -492,8 +523,8 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
     group = workload_group(wl, a.in_flight)              # this workload + its replicas (same weights, own handle / arena / stream)
     flight = InFlight([step] + [w.reverse_step(batch) for w in group[1:]], device)
     vae_m = None
-    # the VAE exists only where something decodes: rank 0's separate vae_decode leg, or every rank under --gather images
-    if (rank == 0 and not a.no_vae and primary) or a.gather == "images":
+    # the VAE exists only where something decodes: rank 0's separate vae_decode leg (--full), or every rank under --gather images
+    if (rank == 0 and not a.no_vae and primary and a.full) or a.gather == "images":
         from invertible_cd_amd import synthetic, vae as vae_mod
         vcfg = vae_mod.SD_VAE if arch == "sd15" else vae_mod.SDXL_VAE
         vsd = synthetic.synthetic_vae_state_dict(vcfg, seed=0, device=device, dtype=torch.float16)
@@ -504,22 +535,37 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
         return to_uint8_images(vae_m.decode((lat.float() / vae_m.config.scaling_factor).clamp(-30, 30))["sample"])
 
     decode = decode_u8 if a.gather == "images" else None
-    for _ in range(max(0, warmup - 1)):
-        step()
-    fam_table = dominant = None
-    if not a.no_profile:
-        fam_table, dominant = family_table(step)          # the last warm-up pass
-    elif warmup:
-        step()
-    if decode is not None:
-        decode_u8(step()[:2])
-    # Pass A = K steps, one batch at a time, with HIP events around the dominant family (the roofline: per-launch durations of the kernel,
-    # undisturbed by a second stream); pass B = K steps with no events at all and `--in-flight` batches in flight.  `value` is pass B -
-    # unless one batch is in flight and the events cost less than 1 % (then pass A, and the roofline IS the timed region's).
-    dt_ev = prof = None
-    if not a.no_profile:
-        dt_ev, _, prof, _ = time_leg(step, steps, 0, batch, device, world, rank, decode, events_family=dominant)
-    dt_plain, per_rank, _, last = time_leg(flight, steps, 1 if len(flight) > 1 else 0, batch, device, world, rank, decode)
+    fam_table = dominant = dt_ev = prof = None
+    if a.full:
+        for _ in range(max(0, warmup - 1)):
+            step()
+        if not a.no_profile:
+            fam_table, dominant = family_table(step)          # the last warm-up pass
+        elif warmup:
+            step()
+        if decode is not None:
+            decode_u8(step()[:2])
+        # Pass A = K steps, one batch at a time, with HIP events around the dominant family (the roofline: per-launch durations of the kernel,
+        # undisturbed by a second stream); pass B = K steps with no events at all and `--in-flight` batches in flight.  `value` is pass B -
+        # unless one batch is in flight and the events cost less than 1 % (then pass A, and the roofline IS the timed region's).
+        if not a.no_profile:
+            dt_ev, _, prof, _ = time_leg(step, steps, 0, batch, device, world, rank, decode, events_family=dominant)
+        dt_plain, per_rank, _, last = time_leg(flight, steps, 1 if len(flight) > 1 else 0, batch, device, world, rank, decode)
+    else:
+        # a plain run times pass B alone; its W warm-up steps go through the batches in flight, rounded up to whole rounds so that every
+        # executor replica has run (and probed its precision level) before the clock starts
+        if warmup:
+            warm = flight.run(-(-warmup // len(flight)) * len(flight))
+            if decode is not None:
+                decode_u8(warm[-1][:2])
+            del warm
+        dt_plain, per_rank, _, last = time_leg(flight, steps, 0, batch, device, world, rank, decode)
+    if a.dump_outputs and primary and rank == 0:
+        # what a caller of the timed path receives from its last step: the latents (and, under --gather images, their uint8 images)
+        arrays = {"latents": last}
+        if decode is not None:
+            arrays["images"] = decode(last.to(torch.float16))
+        dump_outputs(a.dump_outputs, arrays)
     ev_over = (dt_ev - dt_plain) / dt_plain if dt_ev else None
     use_plain = dt_ev is None or ev_over > 0.01 or len(flight) > 1
     dt = dt_plain if use_plain else dt_ev
@@ -527,7 +573,7 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
     # N > 1: the reference's payload - uint8 images + int64 ids in ONE all-gather (running/sd1.5/generate.py:372-383) -
     # timed on its own after the timed region (the per-rank VAE decode before it is the separate vae_decode leg)
     image_gather = None
-    if world > 1 and primary and a.gather != "images":
+    if world > 1 and primary and a.gather != "images" and a.full:
         # (the payload's content does not matter to the collective: uint8 noise of the image shape, so that no rank builds a VAE for it)
         side = 512 if arch == "sd15" else 1024
         u8 = torch.randint(0, 256, (batch, side, side, 3), device=device, dtype=torch.uint8)
@@ -543,7 +589,7 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
 
     # the same loop with the reference's CFG-doubled batching (uncond rows computed and discarded), for the record
     ref_batching = None
-    if arch == "sd15" and rank == 0 and primary and not a.no_ref_batching:
+    if arch == "sd15" and rank == 0 and primary and not a.no_ref_batching and a.full:
         wl.solver.eliminate_dead_uncond = False
         step(); torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -558,7 +604,7 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
     fp16_stream = None
     prec = precision_of(a, wl.net)
     accurate_level = None
-    if a.residual != 0 and not a.no_profile:
+    if a.residual != 0 and not a.no_profile and a.full:
         for w in group:
             w.net.set_option("residual", 0)
         n_alt = max(2, steps // 2)
@@ -581,7 +627,7 @@ def run_reverse(a, wl, arch, batch, steps, warmup, device, world, rank, primary)
     # VAE decode of one step's latents, timed separately ("VAE decode ... reported separately"); it is
     # NOT part of `value` unless --gather images.  SDXL latents are 128x128 -> 1024x1024 images.
     vae_leg = None
-    if rank == 0 and not a.no_vae and primary and vae_m is not None:
+    if rank == 0 and not a.no_vae and primary and vae_m is not None and a.full:
         lat = (last.float() / vae_m.config.scaling_factor).clamp(-30, 30)
         vae_m.decode(lat[:2]); torch.cuda.synchronize()
         tv = time.perf_counter()
@@ -772,7 +818,7 @@ def main():
         if dist.is_initialized():
             dist.destroy_process_group()
     batch = a.batch or (32 if a.arch == "sd15" else 8)
-    default_run = a.arch == "sd15" and not a.batch
+    default_run = a.full and a.arch == "sd15" and not a.batch          # --full: every BASELINE configuration rides on the line
     wl = (SD15Workload if a.arch == "sd15" else SDXLWorkload)(device)
     if a.leg == "edit":                                 # child pass of live_traffic(leg="edit"): the edit leg alone, then out
         e = run_edit(a, wl, a.arch, a.batch or (8 if a.arch == "sd15" else 16), 1, 1, device, world, rank)
@@ -818,7 +864,7 @@ def main():
         out["sdxl"] = {k: sdxl[k] for k in keep if k in sdxl}
     if sdxl_edit is not None:
         out["sdxl_edit"] = sdxl_edit
-    if world == 1 and not a.no_live_traffic and not a.no_profile and out.get("roofline"):
+    if world == 1 and a.full and not a.no_live_traffic and not a.no_profile and out.get("roofline"):
         # roofline.traffic of the PRIMARY line measured in this run (child rocprofv3 passes, after every timed leg, ~17 s for SD1.5); the
         # committed summary stays as the fallback, and as the source of the "sdxl" object's figure (building the 2.6 G-parameter workload
         # under the counter profiler takes minutes - too long for the default run)
@@ -848,7 +894,7 @@ def main():
                                "traffic_kernels_sha": er["kernels_sha"], "traffic_seconds": round(info, 1)})
                 else:
                     er["traffic_live_error"] = info
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.arch, None, cfg_for_cpu)
     print(json.dumps(out), file=_REAL_STDOUT, flush=True)
 

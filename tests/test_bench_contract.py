@@ -1,5 +1,5 @@
 """The bench line the driver parses, checked on the committed evidence (profiles/r05_bench_default.json is the stdout of
-`python bench.py --steps 20 --warmup 5` on an MI355X): every key of the contract is there, with the types and relations the contract states."""
+`python bench.py --full --steps 20 --warmup 5` on an MI355X): every key of the contract is there, with the types and relations the contract states."""
 import json
 import os
 
@@ -98,3 +98,64 @@ def test_committed_traffic_summaries_were_measured_on_the_current_kernel_sources
         assert traffic and source.startswith("profiles/r"), (arch, source)
         if sha != bench.csrc_sha():              # reported, not red: kernels move during a round, the evidence follows at its end
             pytest.skip(f"{source} was measured on kernel sources {sha}, csrc/ is now {bench.csrc_sha()}: re-run tools/profile_round.sh")
+
+
+def _bench():
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    return bench
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain `bench.py` run times the headline leg only; --full adds every other measurement.  --steps sets the timed steps."""
+    bench = _bench()
+    a = bench.parse(["--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse(["--full", "--dump-outputs", "out_dir"])
+    assert a.full is True and a.dump_outputs == "out_dir"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float32_within_the_size_limit(tmp_path):
+    import numpy as np
+    import torch
+    bench = _bench()
+    small = torch.randn(3, 4, 8, 8, generator=torch.Generator().manual_seed(0)).half()
+    big = torch.arange(10000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": small, "big": big}, limit=16000)
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4, 8, 8) and np.array_equal(got, small.float().numpy())
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float64 and b.nbytes <= 8000 and np.all(np.diff(b) > 0)      # a sorted sample of the elements, within its share
+    bench.dump_outputs(str(tmp_path / "b"), {"latents": small, "big": big}, limit=16000)
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))                      # the same sample on every run
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: one JSON line with ms_per_step over exactly K steps, none of the --full
+    objects, and the last timed step's latents in DIR - identical from run to run (the inputs are seeded)."""
+    import subprocess
+    import sys
+    import numpy as np
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, out[:5]
+        lines.append(json.loads(out[0]))
+        dumps.append(np.load(d / "latents.npy"))
+    for d in lines:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["config"]["per_gpu_batch"] == 2 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 2 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+        for k in ("roofline", "cpu_baseline", "edit", "sdxl", "sdxl_edit", "fp16_stream", "vae_decode"):
+            assert k not in d, k
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 4, 64, 64) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])

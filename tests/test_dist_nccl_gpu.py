@@ -101,7 +101,7 @@ def test_bench_under_torchrun_runs_its_counter_passes_live():
         pytest.skip("rocprofv3 not installed")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "4",
-           "--no-cpu-baseline", "--no-vae", "--no-ref-batching", "--no-sdxl", "--no-edit"]
+           "--full", "--no-cpu-baseline", "--no-vae", "--no-ref-batching", "--no-sdxl", "--no-edit"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])

@@ -9,7 +9,7 @@ bash tools/profile_round.sh r06 > $OUT/profile_round.log 2>&1
 python tools/precision_gap.py 2>/dev/null | grep -v amdgpu > $OUT/r06_precision_gap.txt
 python tools/shape_profile.py --arch sd15 --batch 32 2>/dev/null | grep -v amdgpu > $OUT/r06_shapes_sd15_b32.txt
 python tools/shape_profile.py --arch sdxl --batch 8 2>/dev/null | grep -v amdgpu > $OUT/r06_shapes_sdxl_b8.txt
-B="--steps 8 --warmup 3 --no-cpu-baseline --no-vae --no-ref-batching --no-sdxl --no-edit --no-live-traffic --no-profile"
+B="--full --steps 8 --warmup 3 --no-cpu-baseline --no-vae --no-ref-batching --no-sdxl --no-edit --no-live-traffic --no-profile"
 for arch in sd15 sdxl; do for n in 1 2 3; do
 python bench.py --arch $arch $B --in-flight $n 2>/dev/null | python -c "
 import sys, json
@@ -19,7 +19,7 @@ python -m pytest tests -m gpu -q -s --durations=15 2>&1 | grep -v '^$' > $OUT/r0
 tail -30 $OUT/r06_parity.txt
 cat $OUT/r06_in_flight.txt $OUT/r06_precision_gap.txt
 # the whole round's GEMM work against the lockstep tiles of rounds 1 - 5, two batches in flight, alternating, same box
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-vae --no-ref-batching --no-sdxl --no-edit --no-live-traffic"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-vae --no-ref-batching --no-sdxl --no-edit --no-live-traffic"
 for r in 1 2; do for arch in sd15 sdxl; do for t in 0 0x20000000; do
 python bench.py --arch $arch $B --gemm-tune $t 2>/dev/null | python -c "
 import sys, json
