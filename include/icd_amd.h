@@ -267,7 +267,11 @@ typedef struct {
     int32_t edit_count;           /* number of edited prompts the caller built edit_At / edit_D (or planned self_from_base) for; when > 0 the launch
                                    * is rejected unless it equals B - first_cond_sample - 1 (the kernel indexes the operators by sample: a caller
                                    * whose conditional samples are not exactly [base | edit_count edited prompts] must not use this epilogue) */
-    int32_t reserved0;
+    int32_t group_count;          /* prompt groups (0 or 1: the single group above).  G > 1: the conditional samples are G groups of edit_count + 1
+                                   * samples [g0: base, edits | g1: base, edits | ...] (independent images edited in one batch); within group g
+                                   * edit_At / edit_D are indexed [g][edit] ([G * edit_count][96][80] / [G * edit_count][96]), self_from_base reads
+                                   * the q and k of the group's own base sample, acc stays per row.  Rejected unless edit_count > 0 and
+                                   * B - first_cond_sample == G * (edit_count + 1). */
 } icd_probs_epilogue;
 int icd_attention_probs_ex(const void* q, const void* q_carry, const void* k, const void* k_carry, void* probs, int32_t B, int32_t H,
                            int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale,
@@ -324,6 +328,12 @@ int icd_conv_out_n(const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, 
  * (invertible_cd_amd/p2p.py).  The product runs on the matrix cores with fp32 accumulation. */
 int icd_p2p_cross_edit(void* probs, int32_t n_prompts, int32_t heads, int64_t nq, int32_t nk, int32_t ld, const void* At,
                        const float* D, void* stream);
+/* The same for n_groups independent prompt groups in one launch (batched editing of several images): probs fp16
+ * [n_groups * n_prompts * heads, nq, ld], group g's rows [g*n_prompts*heads, (g+1)*n_prompts*heads) edited against ITS base prompt with
+ * operators At[g*(n_prompts-1) + e] / D[g*(n_prompts-1) + e] (fp16 [n_groups*(n_prompts-1), 96, 80] / fp32 [n_groups*(n_prompts-1), 96]).
+ * n_groups = 1 is icd_p2p_cross_edit, bit for bit. */
+int icd_p2p_cross_edit_groups(void* probs, int32_t n_groups, int32_t n_prompts, int32_t heads, int64_t nq, int32_t nk, int32_t ld,
+                              const void* At, const float* D, void* stream);
 
 /* LocalBlend (utils/p2p.py:18-44) in one launch: word-weighted mean over layers x heads of the res x res cross-attention maps
  * of each prompt -> 3x3 max pool -> (nearest resize to the latent) -> normalise by the maximum -> threshold th_pool, OR-ed with
@@ -335,6 +345,16 @@ int icd_p2p_cross_edit(void* probs, int32_t n_prompts, int32_t heads, int64_t nq
 int icd_local_blend(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_prompts, int32_t res,
                     int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, float th_pool, float th_sub,
                     const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W, float* out, void* stream);
+/* LocalBlend for n_groups independent prompt groups of n_prompts each in one launch: maps[l] fp16 [n_groups * n_prompts * heads[l],
+ * res*res, ld] and x [n_groups * n_prompts, C, H, W] group-major; alpha / alpha_sub fp32 [n_groups * n_prompts][n_words].  Group g works
+ * exactly as icd_local_blend on its own rows: masks OR-ed with ITS base prompt's, out[g*P + p] = x[g*P] + m * (x[g*P + p] - x[g*P]) with
+ * its own thresholds th_pool[g] / th_sub[g] (HOST arrays).  flags (HOST array, per group): bit 0 active - an inactive group (start_blend
+ * not reached, or no LocalBlend) is copied, out = x; bit 1: the group has substruct words (alpha_sub rows used; alpha_sub may be NULL
+ * when no group has them).  n_groups = 1 with flags 1 (3) is icd_local_blend, bit for bit. */
+int icd_local_blend_groups(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
+                           int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
+                           const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
+                           float* out, void* stream);
 /* dst[t][i] += src[t][i] (fp16, rounded like torch's in-place add) for up to 32 tensors in one launch: the per-step accumulation
  * of AttentionStore.between_steps (utils/p2p.py:164-170).  dst / src / counts are HOST arrays; tensors 16-byte aligned. */
 int icd_accumulate_multi(void* const* dst, const void* const* src, const int64_t* counts, int32_t n_tensors, void* stream);

@@ -758,12 +758,15 @@ __device__ __forceinline__ f16x8 carry8_as_f16(const u32x2 w) {
 //     probabilities of its query tile (<= 96 keys: a few MFMAs), uses them - rounded to fp16 as the two-pass form reads them from memory -
 //     as the MFMA B operand straight from the accumulator layout, and combines with its own probabilities through the LDS patch that
 //     already stages the rows for the store.  Same operands in the same order as icd_p2p_cross_edit: the same bits.
-// The samples of the launch are [b0 unrelated samples (the unconditional half of a CFG-doubled batch) | base prompt | edited prompts ...].
+// The samples of the launch are [b0 unrelated samples (the unconditional half of a CFG-doubled batch) | base prompt | edited prompts ...],
+// or, with prompt groups (icd_probs_epilogue.group_count), [b0 unrelated samples | group 0: base, edits | group 1: base, edits | ...]: every
+// group's edited prompts take their own base prompt's q / k / probabilities and their own operators (At / D indexed [group][edit]).
 struct ProbsEpi {
     half_t* acc;            // [ (B - b0) * H, Nq, ldp ] or null
-    const half_t* At;       // [nedit][96][80] fp16 (ops.p2p_pack_operator) or null
-    const float* D;         // [nedit][96]
+    const half_t* At;       // [groups * nedit][96][80] fp16 (ops.p2p_pack_operator) or null
+    const float* D;         // [groups * nedit][96]
     int b0, self_base;
+    int P;                  // samples per group (B - b0 for one group)
 };
 
 template <int KS, bool SPLIT = false, int EPI = 0, bool FEW = false>     // EPI: 0 none, 1 store += P / self replacement, 2 also the cross edit
@@ -781,8 +784,12 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
     for (int e = 0; e < 8; ++e) z8[e] = (half_t)0.f;
     constexpr int KF = SPLIT ? 2 * KS : KS;            // fragments per operand: [hi (KS) | lo (KS)]
     const u32x2 zc = {0u, 0u};
-    const int jp = EPI && b >= ep.b0 ? b - ep.b0 : 0;  // prompt index among the conditional samples (0 = the base prompt)
-    const int bq = EPI && ep.self_base && jp > 0 ? ep.b0 : b;       // the sample whose q and k this block reads
+    // per block (scalar): conditional sample r = b - b0 -> group grp = r / P, prompt jp = r % P inside it (0 = the group's base prompt)
+    const int r0 = EPI && b >= ep.b0 ? b - ep.b0 : 0;
+    const int grp = EPI ? __builtin_amdgcn_readfirstlane(r0 / ep.P) : 0;
+    const int jp = r0 - grp * (EPI ? ep.P : 0);
+    const int gb = EPI ? ep.b0 + grp * ep.P : 0;      // the group's base sample
+    const int bq = EPI && ep.self_base && jp > 0 ? gb : b;          // the sample whose q and k this block reads
     // q fragments: the carry stays packed (two registers per fragment, widened to fp16 where an MFMA takes it: two v_perm per use)
     struct QFrags { f16x8 hi[KS]; u32x2 lo[SPLIT ? KS : 1]; };
     auto load_q = [&](QFrags& qq, int bs) {
@@ -842,7 +849,7 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
         return __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     };
     half_t* Pb = a.p + ((long long)bh * a.Nq + q0) * a.ldp;
-    half_t* Ab = EPI && ep.acc && b >= ep.b0 ? ep.acc + ((long long)(jp * a.H + h) * a.Nq + q0) * a.ldp : nullptr;
+    half_t* Ab = EPI && ep.acc && b >= ep.b0 ? ep.acc + ((long long)(r0 * a.H + h) * a.Nq + q0) * a.ldp : nullptr;
     // one k-tile of probabilities (this lane: query lr, keys 32kt + 16j + 8lh .. +7, j = 0, 1) -> patch -> global rows
     auto emit = [&](const f32x16& pv, int kt) {
 #pragma unroll
@@ -915,9 +922,9 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
         f16x8 pb[5];                                       // the base prompt's probabilities of this query tile as the MFMA B operand
         if (EPI == 2 && edit) {                            // (before this block's own q is loaded: one set of q fragments live at a time)
             QFrags qb;
-            load_q(qb, ep.b0);
+            load_q(qb, gb);
             f32x16 sb[3];
-            probs3(sb, qb, ep.b0);
+            probs3(sb, qb, gb);
 #pragma unroll
             for (int ks = 0; ks < 5; ++ks)
 #pragma unroll
@@ -935,14 +942,15 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
                 if (EPI == 2 && edit) {
                     // new[n] = sum_w At[n][w] base[w] + D[n] cur[n] for the 32 tokens of this tile; cur comes back from the patch in
                     // the accumulator layout (row lr, tokens 8g + 4lh .. +3)
-                    const half_t* Ae = ep.At + (long long)(jp - 1) * (96 * 80);
+                    const int eo = grp * (ep.P - 1) + jp - 1;                // operator [group][edit]
+                    const half_t* Ae = ep.At + (long long)eo * (96 * 80);
                     f32x16 acc;
 #pragma unroll
                     for (int ks = 0; ks < 5; ++ks) {
                         const f16x8 af = *reinterpret_cast<const f16x8*>(Ae + (kt * 32 + lr) * 80 + ks * 16 + lh * 8);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, pb[ks], ks == 0 ? zero16 : acc, 0, 0, 0);
                     }
-                    const float* De = ep.D + (long long)(jp - 1) * 96 + kt * 32;
+                    const float* De = ep.D + (long long)eo * 96 + kt * 32;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int n = 8 * g + 4 * lh;
@@ -1137,7 +1145,7 @@ static int attention_probs_run(const void* q, const void* qc, const void* k, con
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldp = ldp;
     a.scale_log2 = scale * 1.4426950408889634f;
     a.qc = (const unsigned char*)qc; a.kc = (const unsigned char*)kc;
-    ProbsEpi ep{nullptr, nullptr, nullptr, 0, 0};
+    ProbsEpi ep{nullptr, nullptr, nullptr, 0, 0, 1};
     if (epi) {
         ICD_CHECK_ARG(epi->first_cond_sample >= 0 && epi->first_cond_sample < B, "icd_attention_probs_ex: first_cond_sample out of range");
         ICD_CHECK_ARG(!epi->edit_At || (epi->edit_D && Nk <= 80 && ldp <= 96),
@@ -1146,8 +1154,13 @@ static int attention_probs_run(const void* q, const void* qc, const void* k, con
         ep.b0 = epi->first_cond_row > 0 ? (int)(epi->first_cond_row / H) : epi->first_cond_sample; ep.self_base = epi->self_from_base != 0;
         ICD_CHECK_ARG(epi->first_cond_row % H == 0 && ep.b0 < B, "icd_attention_probs_ex: first_cond_row must be a multiple of H inside the batch");
         ICD_CHECK_ARG(!(ep.At || ep.self_base) || B - ep.b0 >= 2, "icd_attention_probs_ex: an edit needs a base prompt and at least one edited prompt");
-        ICD_CHECK_ARG(epi->edit_count <= 0 || epi->edit_count == B - ep.b0 - 1,
+        const int groups = epi->group_count > 1 ? epi->group_count : 1;
+        ICD_CHECK_ARG(groups == 1 || epi->edit_count > 0, "icd_attention_probs_ex: group_count %d needs edit_count > 0", epi->group_count);
+        ICD_CHECK_ARG(groups > 1 || epi->edit_count <= 0 || epi->edit_count == B - ep.b0 - 1,
                       "icd_attention_probs_ex: edit_count %d does not match the %d edited samples of the launch", epi->edit_count, B - ep.b0 - 1);
+        ICD_CHECK_ARG(groups == 1 || (long long)(B - ep.b0) == (long long)groups * (epi->edit_count + 1),
+                      "icd_attention_probs_ex: %d conditional samples are not %d groups of %d prompts", B - ep.b0, groups, epi->edit_count + 1);
+        ep.P = groups > 1 ? epi->edit_count + 1 : B - ep.b0;
     }
     const bool use_epi = ep.acc || ep.At || ep.self_base;
     const dim3 grid((unsigned)((Nq + 127) / 128), (unsigned)(B * H));

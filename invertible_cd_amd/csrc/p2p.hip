@@ -22,10 +22,15 @@ namespace {
 constexpr int P2P_KS = 5;          // 16-token k-steps  (80 token slots)
 constexpr int P2P_NT = 3;          // 32-token n-tiles  (96 output slots)
 
+// blockIdx.y = prompt group (one image's [base | edits] rows; the groups are contiguous, nedit + 1 prompts each).
 __global__ __launch_bounds__(256) void p2p_cross_edit_kernel(half_t* __restrict__ probs, long long rows, long long group_stride,
                                                               int ld, int nedit, const half_t* __restrict__ At,
                                                               const float* __restrict__ D) {
     const int tid = threadIdx.x, l = tid & 63, lr = l & 31, lh = l >> 5, wv = tid >> 6;
+    const int grp = blockIdx.y;
+    probs += (long long)grp * (nedit + 1) * group_stride;
+    At += (long long)grp * nedit * (P2P_NT * 32) * (P2P_KS * 16);
+    D += (long long)grp * nedit * (P2P_NT * 32);
     const long long row = ((long long)blockIdx.x * 4 + wv) * 32 + lr;
     const bool ok = row < rows;
     f16x8 z8;
@@ -73,39 +78,52 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_kernel(half_t* __restrict_
 //   mask_p = on_0 | on_p ;  with substruct words: mask_p &= ~(sub_0 | sub_p), sub_q = (heat'_q / max heat'_q) > th_sub, no pooling
 //   out[p] = x[0] + float(mask_p, nearest-resized to H x W) * (x[p] - x[0])     (difference in x's dtype, the rest fp32: torch's
 //                                                                               promotion of `base + mask.float() * (x_t - base)`)
+// Prompt groups (batched editing): blockIdx.y = group of P contiguous prompts, every index above relative to the group's first
+// prompt, with the group's own thresholds; an inactive group (flags bit 0 clear) is copied.  Up to BLEND_MAX_GROUPS per launch.
+constexpr int BLEND_MAX_GROUPS = 32;
 struct BlendArgs {
     const half_t* maps[8];
     int heads[8];
     int n_layers, P, res, n_words, ld;
     const float* alpha;          // [P][n_words]
     const float* alpha_sub;      // [P][n_words] or null
-    float th_pool, th_sub;
     const void* x;               // [P][C][H][W] fp16 or fp32
     int x_f32, C, H, W;
     float* out;                  // [P][C][H][W] fp32
+    float th_pool[BLEND_MAX_GROUPS], th_sub[BLEND_MAX_GROUPS];
+    int flags[BLEND_MAX_GROUPS]; // bit 0 active, bit 1 substruct words
 };
 
 __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
     __shared__ float heat[1024], pooled[1024], red[256];
     __shared__ unsigned char mask[1024], on_tmp[1024];
-    const int p = blockIdx.x, tid = threadIdx.x, res2 = a.res * a.res;
+    const int p = blockIdx.x, gl = blockIdx.y, tid = threadIdx.x, res2 = a.res * a.res;
+    const long long per = (long long)a.C * a.H * a.W;
+    const long long q0 = (long long)gl * a.P;                 // the group's base prompt
+    if (!(a.flags[gl] & 1)) {                                  // start_blend not reached / no LocalBlend: x_t unchanged
+        for (long long i = tid; i < per; i += 256) {
+            const long long o = (q0 + p) * per + i;
+            a.out[o] = a.x_f32 ? reinterpret_cast<const float*>(a.x)[o] : (float)reinterpret_cast<const half_t*>(a.x)[o];
+        }
+        return;
+    }
     int total_heads = 0;
     for (int l = 0; l < a.n_layers; ++l) total_heads += a.heads[l];
     for (int i = tid; i < res2; i += 256) mask[i] = 0;
     __syncthreads();
     // pass 0 / 1: main words of prompt 0 / p (pooled, OR-ed into mask); pass 2 / 3: substruct words (cleared from mask)
-    const int npass = a.alpha_sub ? 4 : 2;
+    const int npass = (a.alpha_sub && (a.flags[gl] & 2)) ? 4 : 2;
     unsigned char sub_any = 0;
     for (int pass = 0; pass < npass; ++pass) {
         const int q = (pass & 1) ? p : 0;
         const bool sub = pass >= 2;
         if ((pass & 1) && p == 0) continue;                        // the base prompt's own pass is pass 0 / 2
-        const float* al = (sub ? a.alpha_sub : a.alpha) + (long long)q * a.n_words;
+        const float* al = (sub ? a.alpha_sub : a.alpha) + (q0 + q) * a.n_words;
         for (int pix = tid; pix < res2; pix += 256) {
             float tot = 0.f;
             for (int l = 0; l < a.n_layers; ++l)
                 for (int h = 0; h < a.heads[l]; ++h) {
-                    const half_t* row = a.maps[l] + (((long long)q * a.heads[l] + h) * res2 + pix) * a.ld;
+                    const half_t* row = a.maps[l] + (((q0 + q) * a.heads[l] + h) * res2 + pix) * a.ld;
                     float s = 0.f;
                     for (int w = 0; w < a.n_words; ++w) {
                         const float aw = al[w];
@@ -137,7 +155,7 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
             __syncthreads();
         }
         mx = red[0];
-        const float th = sub ? a.th_sub : a.th_pool;
+        const float th = sub ? a.th_sub[gl] : a.th_pool[gl];
         for (int pix = tid; pix < res2; pix += 256) {
             const bool on = (pooled[pix] / mx) > th;
             if (!sub) mask[pix] |= on ? 1 : 0;
@@ -151,7 +169,6 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
         __syncthreads();
     }
     // blend
-    const long long per = (long long)a.C * a.H * a.W;
     const float sy = (float)a.res / (float)a.H, sx = (float)a.res / (float)a.W;
     for (long long i = tid; i < per; i += 256) {
         const int xw = (int)(i % a.W), yh = (int)((i / a.W) % a.H);
@@ -160,15 +177,15 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
         float base, diff;
         if (a.x_f32) {
             const float* xf = reinterpret_cast<const float*>(a.x);
-            base = xf[i];
-            diff = xf[(long long)p * per + i] - base;
+            base = xf[q0 * per + i];
+            diff = xf[(q0 + p) * per + i] - base;
         } else {
             const half_t* xh = reinterpret_cast<const half_t*>(a.x);
-            const half_t b = xh[i];
+            const half_t b = xh[q0 * per + i];
             base = (float)b;
-            diff = (float)(half_t)((float)xh[(long long)p * per + i] - base);      // the subtraction happens in fp16 in torch
+            diff = (float)(half_t)((float)xh[(q0 + p) * per + i] - base);      // the subtraction happens in fp16 in torch
         }
-        a.out[(long long)p * per + i] = base + m * diff;
+        a.out[(q0 + p) * per + i] = base + m * diff;
     }
 }
 
@@ -190,37 +207,61 @@ __global__ __launch_bounds__(256) void accumulate_multi_kernel(AccumArgs a) {
 
 }  // namespace
 
-extern "C" int icd_p2p_cross_edit(void* probs, int32_t n_prompts, int32_t heads, int64_t nq, int32_t nk, int32_t ld,
-                                  const void* At, const float* D, void* stream) {
+extern "C" int icd_p2p_cross_edit_groups(void* probs, int32_t n_groups, int32_t n_prompts, int32_t heads, int64_t nq, int32_t nk,
+                                         int32_t ld, const void* At, const float* D, void* stream) {
     ICD_CHECK_ARG(probs && At && D, "icd_p2p_cross_edit: null pointer");
+    ICD_CHECK_ARG(n_groups >= 1 && n_groups <= 65535, "icd_p2p_cross_edit_groups: 1 .. 65535 groups (got %d)", n_groups);
     ICD_CHECK_ARG(n_prompts >= 2 && heads > 0 && nq > 0, "icd_p2p_cross_edit: need a base prompt and at least one edit");
     ICD_CHECK_ARG(nk > 0 && nk <= 80 && ld >= 80 && ld % 8 == 0,
                   "icd_p2p_cross_edit: tokens <= 80, row stride >= 80 and a multiple of 8 (got %d, %d)", nk, ld);
     const long long rows = (long long)heads * nq;
-    hipLaunchKernelGGL(p2p_cross_edit_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(p2p_cross_edit_kernel, dim3((unsigned)((rows + 127) / 128), (unsigned)n_groups), dim3(256), 0, (hipStream_t)stream,
                        (half_t*)probs, rows, rows * ld, ld, n_prompts - 1, (const half_t*)At, D);
     ICD_CHECK_LAUNCH("icd_p2p_cross_edit");
+    return ICD_OK;
+}
+
+extern "C" int icd_p2p_cross_edit(void* probs, int32_t n_prompts, int32_t heads, int64_t nq, int32_t nk, int32_t ld,
+                                  const void* At, const float* D, void* stream) {
+    return icd_p2p_cross_edit_groups(probs, 1, n_prompts, heads, nq, nk, ld, At, D, stream);
+}
+
+extern "C" int icd_local_blend_groups(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
+                                      int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
+                                      const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
+                                      float* out, void* stream) {
+    ICD_CHECK_ARG(maps && heads && alpha && x && out && th_pool && th_sub && flags, "icd_local_blend: null pointer");
+    ICD_CHECK_ARG(n_layers > 0 && n_layers <= 8 && n_groups > 0 && n_prompts > 0 && res > 0 && res * res <= 1024 && n_words > 0 && ld >= n_words,
+                  "icd_local_blend: 1..8 layers, res*res <= 1024, ld >= n_words");
+    ICD_CHECK_ARG(C > 0 && H > 0 && W > 0, "icd_local_blend: empty latent");
+    for (int l = 0; l < n_layers; ++l) ICD_CHECK_ARG(maps[l] && heads[l] > 0, "icd_local_blend: layer %d has no maps", l);
+    for (int g = 0; g < n_groups; ++g)
+        ICD_CHECK_ARG(!(flags[g] & 2) || alpha_sub, "icd_local_blend_groups: group %d has substruct words but alpha_sub is NULL", g);
+    const long long per = (long long)C * H * W;
+    for (int g0 = 0; g0 < n_groups; g0 += BLEND_MAX_GROUPS) {      // (launches in chunks of the groups the argument block holds)
+        const int ng = std::min(n_groups - g0, BLEND_MAX_GROUPS);
+        const long long s0 = (long long)g0 * n_prompts;            // first prompt of the chunk
+        BlendArgs a{};
+        for (int l = 0; l < n_layers; ++l) {
+            a.maps[l] = (const half_t*)maps[l] + s0 * heads[l] * res * res * ld; a.heads[l] = heads[l];
+        }
+        a.n_layers = n_layers; a.P = n_prompts; a.res = res; a.n_words = n_words; a.ld = ld;
+        a.alpha = alpha + s0 * n_words; a.alpha_sub = alpha_sub ? alpha_sub + s0 * n_words : nullptr;
+        a.x = x_is_f32 ? (const void*)((const float*)x + s0 * per) : (const void*)((const half_t*)x + s0 * per);
+        a.x_f32 = x_is_f32; a.C = C; a.H = H; a.W = W; a.out = out + s0 * per;
+        for (int g = 0; g < ng; ++g) { a.th_pool[g] = th_pool[g0 + g]; a.th_sub[g] = th_sub[g0 + g]; a.flags[g] = flags[g0 + g]; }
+        hipLaunchKernelGGL(local_blend_kernel, dim3(n_prompts, ng), dim3(256), 0, (hipStream_t)stream, a);
+        ICD_CHECK_LAUNCH("icd_local_blend");
+    }
     return ICD_OK;
 }
 
 extern "C" int icd_local_blend(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_prompts, int32_t res,
                                int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, float th_pool, float th_sub,
                                const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W, float* out, void* stream) {
-    ICD_CHECK_ARG(maps && heads && alpha && x && out, "icd_local_blend: null pointer");
-    ICD_CHECK_ARG(n_layers > 0 && n_layers <= 8 && n_prompts > 0 && res > 0 && res * res <= 1024 && n_words > 0 && ld >= n_words,
-                  "icd_local_blend: 1..8 layers, res*res <= 1024, ld >= n_words");
-    ICD_CHECK_ARG(C > 0 && H > 0 && W > 0, "icd_local_blend: empty latent");
-    BlendArgs a{};
-    for (int l = 0; l < n_layers; ++l) {
-        ICD_CHECK_ARG(maps[l] && heads[l] > 0, "icd_local_blend: layer %d has no maps", l);
-        a.maps[l] = (const half_t*)maps[l]; a.heads[l] = heads[l];
-    }
-    a.n_layers = n_layers; a.P = n_prompts; a.res = res; a.n_words = n_words; a.ld = ld;
-    a.alpha = alpha; a.alpha_sub = alpha_sub; a.th_pool = th_pool; a.th_sub = th_sub;
-    a.x = x; a.x_f32 = x_is_f32; a.C = C; a.H = H; a.W = W; a.out = out;
-    hipLaunchKernelGGL(local_blend_kernel, dim3(n_prompts), dim3(256), 0, (hipStream_t)stream, a);
-    ICD_CHECK_LAUNCH("icd_local_blend");
-    return ICD_OK;
+    const int32_t flags = 1 | (alpha_sub ? 2 : 0);
+    return icd_local_blend_groups(maps, heads, n_layers, 1, n_prompts, res, n_words, ld, alpha, alpha_sub, &th_pool, &th_sub, &flags, x,
+                                  x_is_f32, C, H, W, out, stream);
 }
 
 extern "C" int icd_accumulate_multi(void* const* dst, const void* const* src, const int64_t* counts, int32_t n_tensors, void* stream) {

@@ -27,25 +27,61 @@ from . import p2p
 def runner(model, prompt, controller, solver, is_cons_forward=False, num_inference_steps=50, guidance_scale=7.5,
            generator=None, latent=None, uncond_embeddings=None, start_time=50, return_type='image',
            dynamic_guidance=False, tau1=0.4, tau2=0.6, w_embed_dim=0):
-    """utils/generation.py:12-66.  Returns (image | latents, the [1,4,64,64] initial latent)."""
+    """utils/generation.py:12-66.  Returns (image | latents, the [1,4,64,64] initial latent).
+
+    Batched editing: `prompt` may be a list of G lists of P prompts (one image's [source, edit_1, ...] each) with a
+    p2p.ControllerBatch of G members and `latent` [G, 4, 64, 64] (or None: G draws from `generator` in one call).  Each group's
+    latent is repeated P times (init_latent per group), per-step `uncond_embeddings` [G, 77, 768] are repeated per group, and the
+    G * P outputs come back group-major, each group as a run of its own would give it.  Returns (images | latents, [G, 4, 64, 64])."""
+    groups = _prompt_groups(prompt, controller)
     p2p.register_attention_control(model, controller)
-    solver.init_prompt(prompt, None)
-    latent, latents = init_latent(latent, model, 512, 512, generator, len(prompt))      # resolution is fixed, :32-34
+    if groups is None:
+        solver.init_prompt(prompt, None)
+        latent, latents = init_latent(latent, model, 512, 512, generator, len(prompt))      # resolution is fixed, :32-34
+    else:
+        G, P = groups
+        solver.init_prompt([p for grp in prompt for p in grp], None)
+        latent, latents = init_latent_groups(latent, model, 512, 512, generator, G, P)
+        if uncond_embeddings is not None:
+            uncond_embeddings = [u.repeat_interleave(P, 0) if u.shape[0] == G else u for u in uncond_embeddings]
     model.scheduler.set_timesteps(num_inference_steps)
     dynamic_guidance = tau1 < 1.0                      # the argument is overridden and tau2 is never looked at (:36)
-    if is_cons_forward:
-        trajectory = solver.cons_generation(latents, guidance_scale=guidance_scale, w_embed_dim=w_embed_dim,
-                                            dynamic_guidance=dynamic_guidance, tau1=tau1, tau2=tau2, controller=controller)
-    else:
-        trajectory = solver.ddim_loop(latents, num_inference_steps, is_forward=False, guidance_scale=guidance_scale,
-                                      dynamic_guidance=dynamic_guidance, tau1=tau1, tau2=tau2, w_embed_dim=w_embed_dim,
-                                      uncond_embeddings=uncond_embeddings, controller=controller)
+    prev_groups, solver.prompt_groups = getattr(solver, "prompt_groups", None), groups
+    try:
+        if is_cons_forward:
+            trajectory = solver.cons_generation(latents, guidance_scale=guidance_scale, w_embed_dim=w_embed_dim,
+                                                dynamic_guidance=dynamic_guidance, tau1=tau1, tau2=tau2, controller=controller)
+        else:
+            trajectory = solver.ddim_loop(latents, num_inference_steps, is_forward=False, guidance_scale=guidance_scale,
+                                          dynamic_guidance=dynamic_guidance, tau1=tau1, tau2=tau2, w_embed_dim=w_embed_dim,
+                                          uncond_embeddings=uncond_embeddings, controller=controller)
+    finally:
+        solver.prompt_groups = prev_groups
     latents = trajectory[-1]
     if return_type == 'image':
         image = latent2image(model.vae, latents.to(model.vae.dtype))
     else:
         image = latents
     return image, latent
+
+
+def _prompt_groups(prompt, controller):
+    """(G, P) for a list of G lists of P prompts (batched editing), None for the reference's flat list."""
+    if isinstance(prompt, str) or not any(isinstance(p, (list, tuple)) for p in prompt):
+        return None
+    if not all(isinstance(p, (list, tuple)) and len(p) > 0 for p in prompt):
+        raise ValueError("runner: a prompt list mixes groups (lists) and single prompts")
+    sizes = {len(p) for p in prompt}
+    if len(sizes) != 1:
+        raise ValueError(f"runner: every prompt group must have the same size (got {sorted(sizes)}); split the batch by size")
+    G, P = len(prompt), sizes.pop()
+    if controller is not None:
+        if not isinstance(controller, p2p.ControllerBatch):
+            raise ValueError("runner: grouped prompts need a p2p.ControllerBatch (one controller per group)")
+        if controller.n_groups != G or (controller.is_edit and controller.n_prompts != P):
+            raise ValueError(f"runner: {G} groups of {P} prompts do not match the ControllerBatch "
+                             f"({controller.n_groups} members of {controller.n_prompts} prompts)")
+    return G, P
 
 
 # ----------------------------------------------------------------------------------------------------------- schedules
@@ -141,6 +177,7 @@ class Generator:
     """Few-step consistency sampler / inverter (utils/generation.py:181-521)."""
 
     eliminate_dead_uncond = True     # skip the unconditional CFG rows when their output is discarded (w_embed_dim > 0)
+    prompt_groups = None             # (G, P) while a batch of G independent prompt groups runs (runner / cons_inversion)
 
     def __init__(self, model, n_steps, noise_scheduler, forward_cons_model=None, reverse_cons_model=None, num_endpoints=1,
                  num_forward_endpoints=1, reverse_timesteps=None, forward_timesteps=None, max_forward_timestep_index=49,
@@ -210,6 +247,15 @@ class Generator:
     # ------------------------------------------------------------------ the UNet call (utils/generation.py:211-253)
     def _w_vector(self, n_doubled, guidance_scale):
         # [0, 0, 0, gs] iff the CFG-doubled batch is exactly 4, else gs everywhere (utils/generation.py:232-235)
+        groups = self.prompt_groups
+        if groups is not None and groups[0] * groups[1] * 2 == n_doubled:
+            # per group, as each group's run of its own would build it: [uncond of every group ; cond of every group]
+            one = self._w_vector_single(2 * groups[1], guidance_scale)
+            return one[:groups[1]] * groups[0] + one[groups[1]:] * groups[0]
+        return self._w_vector_single(n_doubled, guidance_scale)
+
+    @staticmethod
+    def _w_vector_single(n_doubled, guidance_scale):
         if n_doubled == 4:
             return (0.0, 0.0, 0.0, float(guidance_scale))
         return (float(guidance_scale),) * n_doubled
@@ -370,17 +416,33 @@ class Generator:
 
     @torch.no_grad()
     def cons_inversion(self, image, guidance_scale=0.0, w_embed_dim=0, seed=0):
-        """Forward (data -> noise) consistency inversion from a noised encoding at `start_timestep`."""
+        """Forward (data -> noise) consistency inversion from a noised encoding at `start_timestep`.
+
+        `seed` may be a list with one seed per image (batched editing): image g is noised with
+        randn((1, ...), generator=manual_seed(seed[g])) and every row is what an inversion of that image alone with seed[g] gives.
+        An int keeps the one batch-wide draw."""
         alpha_schedule, sigma_schedule = self._schedules()
         latent = self.image2latent(image)
-        noise = torch.randn(latent.shape, generator=torch.Generator().manual_seed(seed)).to(latent.device)
+        groups = None
+        if isinstance(seed, (list, tuple)):
+            if len(seed) != latent.shape[0]:
+                raise ValueError(f"cons_inversion: {len(seed)} seeds for {latent.shape[0]} images")
+            noise = torch.cat([torch.randn((1, *latent.shape[1:]), generator=torch.Generator().manual_seed(int(sd))) for sd in seed])
+            noise = noise.to(latent.device)
+            groups = (latent.shape[0], 1)
+        else:
+            noise = torch.randn(latent.shape, generator=torch.Generator().manual_seed(seed)).to(latent.device)
         latent = self.noise_scheduler.add_noise(latent, noise, torch.tensor([self.start_timestep]))
         image_rec = self.latent2image(latent)
-        with _editing(self.forward_cons_model, True):    # forward steps amplify the per-evaluation error: accurate precision level
-            for t, s in zip(self.forward_timesteps, self.forward_boundary_timesteps):
-                noise_pred = self.get_noise_pred(model=self.forward_cons_model, latent=latent, t=t, context=None,
-                                                 guidance_scale=guidance_scale, w_embed_dim=w_embed_dim, dynamic_guidance=False)
-                latent = self._boundary_step(noise_pred, t, s, latent, alpha_schedule, sigma_schedule)
+        prev_groups, self.prompt_groups = self.prompt_groups, groups
+        try:
+            with _editing(self.forward_cons_model, True):    # forward steps amplify the per-evaluation error: accurate precision level
+                for t, s in zip(self.forward_timesteps, self.forward_boundary_timesteps):
+                    noise_pred = self.get_noise_pred(model=self.forward_cons_model, latent=latent, t=t, context=None,
+                                                     guidance_scale=guidance_scale, w_embed_dim=w_embed_dim, dynamic_guidance=False)
+                    latent = self._boundary_step(noise_pred, t, s, latent, alpha_schedule, sigma_schedule)
+        finally:
+            self.prompt_groups = prev_groups
         return image_rec, [latent]
 
 
@@ -397,6 +459,18 @@ def init_latent(latent, model, height, width, generator, batch_size):
     if latent is None:
         latent = torch.randn((1, model.unet.in_channels, height // 8, width // 8), generator=generator)
     latents = latent.expand(batch_size, model.unet.in_channels, height // 8, width // 8).to(model.device)
+    return latent, latents
+
+
+def init_latent_groups(latent, model, height, width, generator, n_groups, n_prompts):
+    """init_latent per prompt group: G noise samples (one call of the generator when `latent` is None), each repeated for the P
+    prompts of its group -> ([G, 4, h, w], [G * P, 4, h, w] group-major)."""
+    shape = (model.unet.in_channels, height // 8, width // 8)
+    if latent is None:
+        latent = torch.randn((n_groups, *shape), generator=generator)
+    if tuple(latent.shape) != (n_groups, *shape):
+        raise ValueError(f"runner: latent of shape {tuple(latent.shape)} for {n_groups} prompt groups (expected {(n_groups, *shape)})")
+    latents = latent[:, None].expand(n_groups, n_prompts, *shape).reshape(n_groups * n_prompts, *shape).to(model.device)
     return latent, latents
 
 

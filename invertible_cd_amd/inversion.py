@@ -5,6 +5,10 @@ The consistency branch (`is_cons_inversion=True` -> Generator.cons_inversion) is
 UNet.  The DDIM-inversion branch is kept (it reuses the same UNet).  Null-text optimisation (`do_nti=True`,
 utils/inversion.py:11-48) needs autograd THROUGH the UNet, which the inference-only MI355X executor does not provide:
 it raises NotImplementedError (out of scope, baseline only).
+
+Batched editing: G image paths with G prompts invert in one batch ([G, 4, 64, 64]; do_npi: per-step cond embeddings [G, 77, 768]).
+With `seed` a list of G seeds, row g is exactly what `invert` of image g alone with seed=seed[g] returns; an int seed keeps the
+one batch-wide noise draw.
 """
 from .generation import load_512
 from .p2p import register_attention_control

@@ -346,9 +346,10 @@ def attention_fused(q, k, vt, B, H, Nq, Nk, d, scale, causal=False, prescaled=Fa
 
 
 def attention_probs(q, k, B, H, Nq, Nk, d, scale, ld=None, out=None, q_carry=None, k_carry=None, acc=None, edit=None, self_from_base=False,
-                    first_cond_sample=0):
+                    first_cond_sample=0, edit_count=0, group_count=0):
     """P[b*H+h, n, :Nk] = softmax(scale * q.k) as fp16 [B*H, Nq, ld] in one pass (no fp32 score tensor); pad columns zero.
-    q_carry / k_carry: uint8 error carries of q / k (icd_attention_probs_split: scores from hi + lo operands)."""
+    q_carry / k_carry: uint8 error carries of q / k (icd_attention_probs_split: scores from hi + lo operands).
+    group_count G > 1 (with edit_count = P - 1): the conditional samples are G prompt groups of P, each edited against its own base."""
     _chk_rows(q, "q"); _chk_rows(k, "k")
     ld = ld or (Nk + 7) // 8 * 8
     if out is None:
@@ -358,6 +359,7 @@ def attention_probs(q, k, B, H, Nq, Nk, d, scale, ld=None, out=None, q_carry=Non
         # edit = (At, Dp) of p2p_pack_operator, self_from_base: the edited prompts take the base prompt's rows
         epi = _lib.ProbsEpilogue()
         epi.first_cond_sample, epi.self_from_base = first_cond_sample, int(self_from_base)
+        epi.edit_count, epi.group_count = edit_count, group_count
         if acc is not None:
             assert acc.dtype == torch.float16 and acc.is_cuda and acc.stride() == (Nq * ld, ld, 1) and acc.shape[0] == (B - first_cond_sample) * H
             epi.acc = acc.data_ptr()
@@ -453,6 +455,21 @@ def p2p_cross_edit(probs, n_prompts, At, Dp):
     return probs
 
 
+def p2p_cross_edit_groups(probs, n_groups, n_prompts, At, Dp):
+    """p2p_cross_edit for n_groups independent prompt groups in one launch (icd_p2p_cross_edit_groups): probs fp16
+    [n_groups*n_prompts*heads, nq, nk <= 80] group-major, (At, Dp) the groups' packed operators concatenated
+    ([n_groups*(n_prompts-1), 96, 80] / [n_groups*(n_prompts-1), 96])."""
+    assert p2p_cross_edit_supported(probs)
+    bh, nq, nk = probs.shape
+    ne = n_groups * (n_prompts - 1)
+    assert n_groups >= 1 and bh % (n_groups * n_prompts) == 0
+    assert tuple(At.shape) == (ne, 96, 80) and tuple(Dp.shape) == (ne, 96)
+    assert At.dtype == torch.float16 and At.is_contiguous() and Dp.dtype == torch.float32 and Dp.is_contiguous()
+    _lib.check(_lib.load().icd_p2p_cross_edit_groups(_p(probs), n_groups, n_prompts, bh // (n_groups * n_prompts), nq, nk,
+                                                     probs.stride(1), _p(At), _p(Dp), _stream()), "icd_p2p_cross_edit_groups")
+    return probs
+
+
 ACT_SILU, ACT_QUICK_GELU, ACT_GELU = 0, 1, 2
 
 
@@ -533,6 +550,35 @@ def local_blend(maps, alpha, alpha_sub, th_pool, th_sub, x_t, res=16):
     _lib.check(_lib.load().icd_local_blend(ptrs, heads, len(maps), P, res, n_words, ld, _p(al), None if als is None else _p(als),
                                            float(th_pool), float(th_sub), _p(x_t), int(x_t.dtype == torch.float32), x_t.shape[1],
                                            x_t.shape[2], x_t.shape[3], _p(out), _stream()), "icd_local_blend")
+    return out
+
+
+def local_blend_groups(maps, alpha, alpha_sub, th_pool, th_sub, active, x_t, n_groups, res=16):
+    """LocalBlend for n_groups prompt groups of P in one launch (icd_local_blend_groups).  maps: list of <= 8 fp16 cuda tensors
+    [G*P*heads_l, res*res, n_words]; alpha fp32 [G*P, n_words]; alpha_sub fp32 [G*P, n_words] or None, with a list of G booleans
+    (which groups have substruct words) as its companion: alpha_sub = (tensor, has_sub); th_pool / th_sub / active: G values each;
+    x_t [G*P, C, H, W] fp16 / fp32 -> fp32.  Inactive groups come back unchanged."""
+    GP, n_words = alpha.shape
+    assert GP % n_groups == 0 and len(th_pool) == len(th_sub) == len(active) == n_groups
+    P = GP // n_groups
+    assert x_t.is_cuda and x_t.is_contiguous() and x_t.dtype in (torch.float16, torch.float32) and x_t.shape[0] == GP
+    ld = maps[0].stride(1)
+    ptrs, heads = (C.c_void_p * len(maps))(), (C.c_int32 * len(maps))()
+    for i, m in enumerate(maps):
+        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 3 and m.shape[1] == res * res and m.shape[2] == n_words
+        assert m.stride(2) == 1 and m.stride(1) == ld and m.stride(0) == res * res * ld and m.shape[0] % GP == 0
+        ptrs[i], heads[i] = m.data_ptr(), m.shape[0] // GP
+    al = alpha.to(device=x_t.device, dtype=torch.float32).contiguous()
+    als, has_sub = (None, [False] * n_groups) if alpha_sub is None else alpha_sub
+    if als is not None:
+        als = als.to(device=x_t.device, dtype=torch.float32).contiguous()
+        assert tuple(als.shape) == (GP, n_words)
+    tp, ts = (C.c_float * n_groups)(*map(float, th_pool)), (C.c_float * n_groups)(*map(float, th_sub))
+    fl = (C.c_int32 * n_groups)(*[int(bool(a)) | (2 if s else 0) for a, s in zip(active, has_sub)])
+    out = torch.empty(x_t.shape, device=x_t.device, dtype=torch.float32)
+    _lib.check(_lib.load().icd_local_blend_groups(ptrs, heads, len(maps), n_groups, P, res, n_words, ld, _p(al), _p(als), tp, ts, fl,
+                                                  _p(x_t), int(x_t.dtype == torch.float32), x_t.shape[1], x_t.shape[2], x_t.shape[3],
+                                                  _p(out), _stream()), "icd_local_blend_groups")
     return out
 
 

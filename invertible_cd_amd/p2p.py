@@ -80,6 +80,10 @@ class LocalBlend:
         self.counter += 1
         if self.counter <= self.start_blend:
             return x_t
+        return self.blend(x_t, attention_store)
+
+    def blend(self, x_t, attention_store):
+        """The blend itself, past start_blend (what __call__ does after advancing its counter)."""
         n_prompts = self.alpha_layers.shape[0]
         layers = attention_store["down_cross"][2:4] + attention_store["up_cross"][:3]
         if self._on_device(x_t, layers):
@@ -286,6 +290,13 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         super().forward(attn, is_cross, place_in_unet)          # stores a VIEW: the stored tensor sees the edit below
         if getattr(self, "_kernel_edit", False):                # the probability kernel's epilogue has applied this layer's edit already
             return attn
+        return self.edit_rows(attn, is_cross, place_in_unet)
+
+    def self_window(self, step):
+        return self.num_self_replace[0] <= step < self.num_self_replace[1]
+
+    def edit_rows(self, attn, is_cross: bool, place_in_unet: str):
+        """This step's edit of one prompt group's conditional rows [base | edits] x heads (forward after storing the view)."""
         in_self_window = self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]
         if not (is_cross or in_self_window):
             return attn
@@ -375,6 +386,153 @@ def make_controller(prompts: List[str], is_replace_controller: bool, cross_repla
     return controller
 
 
+# ------------------------------------------------------------------------------------------- batched editing
+class ControllerBatch(AttentionStore):
+    """One controller per image for a UNet batch of G independent prompt groups [g0: P samples | g1: P samples | ...] (batched
+    editing: many images edited in one call instead of a stream of batch-P calls).
+
+    Members are the reference-shaped controllers of make_controller (AttentionReplace / Refine / Reweight) with the same number of
+    prompts P, or plain AttentionStores.  The batch keeps ONE store tensor per layer (all groups' rows: the probability kernel's
+    store epilogue keeps working); after every step each member's attention_store holds views of its own rows and its counters
+    (cur_step, cur_att_layer, LocalBlend.counter) stand where a run of its own would have left them, so get_average_attention() and
+    the LocalBlend of every image work per image.  The cross-attention edit is one launch for all groups (icd_p2p_cross_edit_groups,
+    or the probability kernel's epilogue with group_count = G), LocalBlend one launch (icd_local_blend_groups)."""
+
+    EDIT_TYPES = ("AttentionReplace", "AttentionRefine", "AttentionReweight")
+
+    def __init__(self, controllers):
+        members = list(controllers)
+        if not members:
+            raise ValueError("ControllerBatch needs at least one controller")
+        if all(type(c).__name__ in self.EDIT_TYPES and type(c).__module__ == __name__ for c in members):
+            sizes = {c.batch_size for c in members}
+            if len(sizes) != 1:
+                raise ValueError(f"ControllerBatch: every group must have the same number of prompts (got {sorted(sizes)}); split by P")
+            self.n_prompts, self.is_edit = sizes.pop(), True
+        elif all(type(c) is AttentionStore for c in members):
+            self.n_prompts, self.is_edit = None, False
+        else:
+            raise ValueError("ControllerBatch: members must all be make_controller edit controllers or all plain AttentionStores, "
+                             f"got {sorted({type(c).__name__ for c in members})}")
+        self.members = members
+        super().__init__()
+
+    @property
+    def n_groups(self):
+        return len(self.members)
+
+    @property
+    def num_att_layers(self):
+        return self._num_att_layers
+
+    @num_att_layers.setter
+    def num_att_layers(self, n):
+        self._num_att_layers = n
+        for m in self.members:
+            m.num_att_layers = n
+
+    def needs_probs(self, is_cross, n_queries, place_in_unet):
+        return (self.is_edit and is_cross) or n_queries <= self.STORE_MAX_QUERIES
+
+    def self_window(self, step):
+        """True / False when every member is inside / outside its self-replace window at `step`, None when they disagree."""
+        w = {m.self_window(step) for m in self.members}
+        return w.pop() if len(w) == 1 else None
+
+    def cross_edit_operator(self, step, dev):
+        """The members' packed operators of this step concatenated ([G*(P-1), 96, 80] / [G*(P-1), 96]), cached on `dev`."""
+        key = (int(step), str(dev))
+        cache = self.__dict__.setdefault("_edit_ops", {})
+        if key not in cache:
+            ops_ = [m.cross_edit_operator(step, dev) for m in self.members]
+            cache[key] = (torch.cat([a for a, _ in ops_]).contiguous(), torch.cat([d for _, d in ops_]).contiguous())
+        return cache[key]
+
+    def forward(self, attn, is_cross: bool, place_in_unet: str):
+        super().forward(attn, is_cross, place_in_unet)          # one stored view of all groups' rows
+        if not self.is_edit or getattr(self, "_kernel_edit", False):
+            return attn
+        G, P = self.n_groups, self.n_prompts
+        if is_cross and attn.is_cuda:
+            from . import ops
+            if ops.p2p_cross_edit_supported(attn) and attn.shape[0] % (G * P) == 0:
+                At, Dp = self.cross_edit_operator(self.cur_step, attn.device)
+                return ops.p2p_cross_edit_groups(attn, G, P, At, Dp)
+        rows = attn.shape[0] // G
+        for g, m in enumerate(self.members):                     # per group: the member's own edit on its own rows
+            v = attn[g * rows:(g + 1) * rows]
+            new = m.edit_rows(v, is_cross, place_in_unet)
+            if new is not v and new.data_ptr() != v.data_ptr():
+                v.copy_(new)
+        return attn
+
+    def _advance(self):
+        super()._advance()
+        for m in self.members:
+            m.cur_att_layer, m.cur_step = self.cur_att_layer, self.cur_step
+
+    def between_steps(self):
+        super().between_steps()
+        self._share()
+
+    def _share(self):
+        """Every member's store: views of its own rows of the batch's tensors."""
+        G = self.n_groups
+        for g, m in enumerate(self.members):
+            m.attention_store = {key: [t[g * (t.shape[0] // G):(g + 1) * (t.shape[0] // G)] for t in ts]
+                                 for key, ts in self.attention_store.items()}
+            m.step_store = m.get_empty_store()
+            m._fused_acc = set()
+
+    def reset(self):
+        super().reset()
+        for m in self.members:
+            m.reset()
+
+    def step_callback(self, x_t):
+        if not self.is_edit:
+            return x_t
+        G, P = self.n_groups, self.n_prompts
+        if x_t.shape[0] != G * P:
+            raise ValueError(f"ControllerBatch.step_callback: {x_t.shape[0]} latents for {G} groups of {P} prompts")
+        lbs = [m.local_blend for m in self.members]
+        active = []
+        for lb in lbs:                                           # each member's LocalBlend counter advances as in a run of its own
+            if lb is not None:
+                lb.counter += 1
+            active.append(lb is not None and lb.counter > lb.start_blend)
+        if not any(active):
+            return x_t
+        layers = self.attention_store["down_cross"][2:4] + self.attention_store["up_cross"][:3]
+        if LocalBlend._on_device(x_t, layers) and all(lb is None or lb.alpha_layers.shape[0] == P for lb in lbs):
+            from . import ops
+            alpha, sub, th_pool, th_sub = self._blend_terms(lbs, x_t.device)
+            return ops.local_blend_groups(layers, alpha, sub, th_pool, th_sub, active, x_t.contiguous(), G)
+        outs = []
+        for g, (m, lb, on) in enumerate(zip(self.members, lbs, active)):
+            xg = x_t[g * P:(g + 1) * P]
+            outs.append(lb.blend(xg, m.attention_store) if on else xg)
+        return torch.cat(outs)
+
+    def _blend_terms(self, lbs, dev):
+        """(alpha [G*P, 77], (alpha_sub [G*P, 77], has_sub) or None, th_pool [G], th_sub [G]) of the members' LocalBlends, cached."""
+        key = str(dev)
+        cache = self.__dict__.setdefault("_blend_cache", {})
+        if key not in cache:
+            P = self.n_prompts
+            zero = torch.zeros(P, MAX_NUM_WORDS, device=dev)
+            alpha = torch.cat([zero if lb is None else lb.alpha_layers.reshape(P, MAX_NUM_WORDS).to(dev, torch.float32) for lb in lbs])
+            has_sub = [lb is not None and lb.substruct_layers is not None for lb in lbs]
+            sub = None
+            if any(has_sub):
+                sub = (torch.cat([lb.substruct_layers.reshape(P, MAX_NUM_WORDS).to(dev, torch.float32) if h else zero
+                                  for lb, h in zip(lbs, has_sub)]), has_sub)
+            th_pool = [0.0 if lb is None else lb.th[0] for lb in lbs]
+            th_sub = [0.0 if lb is None else lb.th[1] for lb in lbs]
+            cache[key] = (alpha, sub, th_pool, th_sub)
+        return cache[key]
+
+
 # ------------------------------------------------------------------------------------------- registration
 class DummyController:
     """What the reference installs for `controller=None` (utils/p2p.py:356-365)."""
@@ -420,7 +578,7 @@ class HookAdapter:
         # round 5: for the shipped controllers (exactly these classes) what they do to P - accumulate into the store, copy the base prompt's
         # self-attention rows, the cross-attention edit operator - rides in the probability kernel's epilogue (icd_probs_epilogue): one pass
         # over P instead of three.  `controller.fused_epilogue = False` keeps the separate passes (A/B; bit-identical results).
-        self.fuse = (self.native and type(controller) in (AttentionStore, AttentionReplace, AttentionRefine, AttentionReweight)
+        self.fuse = (self.native and type(controller) in (AttentionStore, AttentionReplace, AttentionRefine, AttentionReweight, ControllerBatch)
                      and getattr(controller, "fused_epilogue", True) and not LOW_RESOURCE and str(dev).startswith("cuda"))
         self.epilogue = None
         self._epi_refs = None
@@ -476,7 +634,29 @@ class HookAdapter:
         epi = _lib.ProbsEpilogue()
         epi.first_cond_row = first
         refs = []
-        if isinstance(c, AttentionControlEdit):
+        if isinstance(c, ControllerBatch) and c.is_edit:
+            # G prompt groups of P on the conditional samples: operators [group][edit], each group's self rows from its own base
+            # (group_count = G); a self layer whose members disagree about their self-replace windows takes the separate passes
+            G, P = c.n_groups, c.n_prompts
+            cond = (self.batch if self.cond_only else self.batch // 2) if self.batch > 0 else 0
+            if rows % (G * P) != 0 or P < 2 or cond != G * P:
+                return None
+            epi.edit_count, epi.group_count = P - 1, G
+            if is_cross:
+                if not (nk <= 80 and ld >= 80 and ld % 8 == 0):
+                    return None
+                At, Dp = c.cross_edit_operator(c.cur_step, self.dev)
+                epi.edit_At, epi.edit_D = At.data_ptr(), Dp.data_ptr()
+                refs += [At, Dp]
+                self._epi_edit = True
+            else:
+                win = c.self_window(c.cur_step)
+                if win is None:
+                    return None
+                if win:
+                    epi.self_from_base = 1
+                    self._epi_edit = True
+        elif isinstance(c, AttentionControlEdit):
             # the kernel indexes the edit operators by SAMPLE (prompt jp = sample - first conditional sample, jp - 1 operators), while the
             # controller - like the reference (utils/p2p.py:192-194) - groups the rows by heads = rows / batch_size: the two agree only when
             # the conditional samples of this call are exactly the controller's prompts.  Anything else (more latents than prompts, an
