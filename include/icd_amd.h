@@ -528,6 +528,29 @@ int icd_unet_forward(icd_unet* u, const icd_unet_io* io, void* stream);
 int64_t icd_unet_kv_cache_bytes(const icd_unet* u, int32_t batch, int32_t n_ctx);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Edit-quality metrics (csrc/metrics.hip): what the reference's drivers compute after an edit (running/sd1.5/edit.py "VALIDATION PART",
+ * utils/metrics.py) on images that never leave the device.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* transformers.CLIPImageProcessor on uint8 NHWC images [B, H, W, 3] (device): Pillow's BICUBIC resize to resized_h x resized_w (the
+ * shortest-edge rule is the caller's), centre crop `crop` x `crop`, (u / 255 - mean) / std in fp32, rounded to fp16 and scattered into
+ * the patch matrix the patch-embedding GEMM reads: out [B * (crop / patch)^2, ldo], column (c * patch + py) * patch + px, columns
+ * past 3 * patch^2 zero.  Pillow's resample is integer arithmetic on coefficient tables, so the resized bytes are Pillow's bit for bit:
+ * h_* describe the horizontal pass (W -> resized_w: first tap, tap count [resized_w], coefficients [resized_w, h_taps], int32, on the
+ * device), v_* the vertical one (H -> resized_h); h_taps / v_taps must be the row length Pillow uses for these sizes
+ * (2 * ceil(2 * max(in / out, 1)) + 1).  mean / stdv: 3 floats each on the HOST.  tmp: uint8 [B * H * crop * 3] scratch on the device
+ * (the horizontal pass), 4-byte aligned; out 16-byte aligned; `images` may start at any byte (a slice of a larger batch).  Limits:
+ * W <= 4096 (four image rows are staged in LDS), patch * crop * 3 <= 65536.  Nothing is allocated here.  Two launches. */
+int icd_clip_preprocess(const void* images, int32_t B, int32_t H, int32_t W, int32_t resized_h, int32_t resized_w, int32_t crop,
+                        int32_t patch, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
+                        const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps,
+                        const float* mean, const float* stdv, void* tmp, void* out, int32_t ldo, void* stream);
+/* out[r] = a[r] . b[r] / (|a[r]| |b[r]|) for row-major a, b [rows, D] (fp16, or fp32 when is_f32), fp32 accumulation, one wave per row. */
+int icd_cosine_rows(const void* a, const void* b, int64_t rows, int32_t D, int32_t lda, int32_t ldb, int32_t is_f32, float* out,
+                    void* stream);
+/* out[r] = sum_i (a[r, i] - b[r, i])^2 over uint8 a, b [rows, n], exact, uint64 (PSNR's mean squared error without a rounding). */
+int icd_sq_diff_sum_u8(const void* a, const void* b, int64_t rows, int64_t n, uint64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-kernel-family timing of the executor's launches with HIP events recorded on the launch stream (bench.py's
  * roofline leg).  No reference counterpart (the reference has no timing code at all).
  * ---------------------------------------------------------------------------------------------------------- */

@@ -7,7 +7,7 @@ binding of libicd_amd.so (include/icd_amd.h).  See DESIGN.md / INTEGRATION.md.
 import importlib
 
 __all__ = ["generation", "generation_sdxl", "p2p", "seq_aligner", "inversion", "loading", "dist_utils", "unet", "ops",
-           "synthetic", "schedulers", "pipelines", "unet_config"]
+           "synthetic", "schedulers", "pipelines", "unet_config", "clip", "metrics", "resample"]
 
 
 def __getattr__(name):          # lazy submodule import: `import invertible_cd_amd` stays cheap and GPU-free

@@ -176,6 +176,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_int32, C.c_void_p]),
     "icd_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo)]),
     "icd_unet_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "icd_clip_preprocess": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
+                            + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "icd_cosine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icd_sq_diff_sum_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "icd_profile_enable": (C.c_int, [C.c_int32]),
     "icd_profile_read": (C.c_int, [C.POINTER(ProfileRow), C.c_int32]),
     "icd_profile_dump": (C.c_int, [C.POINTER(ProfileRecord), C.c_int32]),

@@ -1,0 +1,257 @@
+// Edit-quality metrics on the device: CLIP image preprocessing (Pillow's BICUBIC resample, bit for bit), row-wise cosine, and the exact
+// integer sum of squared differences behind PSNR.  All three are bandwidth kernels; the arithmetic is restated from Pillow's
+// documented behaviour (invertible_cd_amd/resample.py builds the coefficient tables).
+#include "common.h"
+
+namespace {
+
+constexpr int PREC_BITS = 32 - 8 - 2;          // Pillow's fixed-point fraction
+constexpr int HROWS = 4;                       // image rows per block of the horizontal pass
+
+__device__ __forceinline__ unsigned clip8(int acc) {
+    const int v = (acc + (1 << (PREC_BITS - 1))) >> PREC_BITS;
+    return (unsigned)min(max(v, 0), 255);
+}
+
+struct PreK {
+    const unsigned char* img;                  // [B, H, W, 3]
+    unsigned char* tmp;                        // [B * H, S, 3]: the horizontal pass, cropped to the S columns that survive
+    half_t* out;                               // [B * G * G, ldo]
+    const int *hfirst, *hcount, *hcoef, *vfirst, *vcount, *vcoef;     // tables, already offset to the crop's first column / row
+    int B, H, W, S, P, G, ldo, hk, vk;
+    long long rows;                            // B * H
+    float mean[3], stdv[3];
+};
+
+// Horizontal pass.  One block owns HROWS consecutive image rows (they are contiguous in memory): 16-byte loads stage them in LDS, every
+// thread then produces 4 consecutive output bytes of one row (taps from LDS) and stores them as one dword.
+__global__ __launch_bounds__(256) void clip_resample_h_kernel(PreK p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const long long r0 = (long long)blockIdx.x * HROWS;
+    const int nrows = (int)min((long long)HROWS, p.rows - r0);
+    const long long rowb = (long long)p.W * 3;
+    const long long total = p.rows * rowb;
+    const long long start = r0 * rowb, end = start + nrows * rowb;
+    // 16-byte chunks are taken at aligned ADDRESSES: the batch may start anywhere (a slice of a larger tensor), and so may its rows
+    const int mis = (int)((uintptr_t)p.img & 15);
+    const long long a0 = (start + mis) & ~15LL;                // offsets from the aligned address below the base
+    const int shift = (int)(start + mis - a0);
+    const int nchunk = (int)((end + mis - a0 + 15) >> 4);
+    const unsigned char* abase = p.img - mis;
+    for (int c = threadIdx.x; c < nchunk; c += blockDim.x) {
+        const long long off = a0 + (long long)c * 16;
+        if (off >= mis && off + 16 <= total + mis) {
+            *reinterpret_cast<uint4*>(lds + c * 16) = *reinterpret_cast<const uint4*>(abase + off);
+        } else {                                               // the first / last bytes of the batch: nothing outside the buffer is read
+            for (int j = 0; j < 16; ++j) lds[c * 16 + j] = (off + j >= mis && off + j < total + mis) ? abase[off + j] : 0;
+        }
+    }
+    __syncthreads();
+    const int wpr = p.S * 3 / 4;                               // output dwords per row
+    for (int it = threadIdx.x; it < nrows * wpr; it += blockDim.x) {
+        const int row = it / wpr, wd = it - row * wpr;
+        const unsigned char* src = lds + shift + (long long)row * rowb;
+        unsigned packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = wd * 4 + j, x = e / 3, c = e - x * 3;
+            const int f = max(p.hfirst[x], 0);
+            const int n = min(p.hcount[x], min(p.hk, p.W - f));     // clamped: a wrong table cannot read outside the row
+            const int* kk = p.hcoef + (long long)x * p.hk;
+            int acc = 0;
+            for (int k = 0; k < n; ++k) acc += kk[k] * (int)src[(f + k) * 3 + c];
+            packed |= clip8(acc) << (8 * j);
+        }
+        *reinterpret_cast<unsigned*>(p.tmp + (r0 + row) * (long long)(p.S * 3) + wd * 4) = packed;
+    }
+}
+
+// Vertical pass + crop + normalise + patch scatter.  One block owns one row of patches (P output rows): the resampled bytes go to LDS,
+// then the G patch-matrix rows leave as 16-byte stores in column order (c * P + py) * P + px, pad columns zero.
+__global__ __launch_bounds__(256) void clip_resample_v_kernel(PreK p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // [P, S * 3]
+    const int b = blockIdx.x / p.G, pr = blockIdx.x - b * p.G;
+    const int rowb = p.S * 3, wpr = rowb / 4;
+    const unsigned char* src = p.tmp + (long long)b * p.H * rowb;
+    for (int it = threadIdx.x; it < p.P * wpr; it += blockDim.x) {
+        const int yy = it / wpr, wd = it - yy * wpr;
+        const int y = pr * p.P + yy;
+        const int f = max(p.vfirst[y], 0);
+        const int n = min(p.vcount[y], min(p.vk, p.H - f));
+        const int* kk = p.vcoef + (long long)y * p.vk;
+        const unsigned char* col = src + (long long)f * rowb + wd * 4;
+        unsigned packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                          // four neighbouring bytes of each tap row: one 4-byte segment per lane
+            int acc = 0;
+            for (int k = 0; k < n; ++k) acc += kk[k] * (int)col[(long long)k * rowb + j];
+            packed |= clip8(acc) << (8 * j);
+        }
+        *reinterpret_cast<unsigned*>(lds + yy * rowb + wd * 4) = packed;
+    }
+    __syncthreads();
+    const int PP = p.P * p.P, cols = 3 * PP, vpr = p.ldo / 8;
+    half_t* out = p.out + ((long long)b * p.G + pr) * p.G * p.ldo;
+    for (int it = threadIdx.x; it < p.G * vpr; it += blockDim.x) {
+        const int px_blk = it / vpr, c8 = (it - px_blk * vpr) * 8;
+        f16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int col = c8 + j;
+            float f = 0.f;
+            if (col < cols) {
+                const int c = col / PP, rem = col - c * PP, py = rem / p.P, px = rem - py * p.P;
+                const float u = (float)lds[py * rowb + (px_blk * p.P + px) * 3 + c];
+                f = (u / 255.0f - p.mean[c]) / p.stdv[c];
+            }
+            v[j] = (half_t)f;
+        }
+        *reinterpret_cast<f16x8*>(out + (long long)px_blk * p.ldo + c8) = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- cosine of rows
+template <typename T>
+__global__ __launch_bounds__(256) void cosine_rows_kernel(const T* a, const T* b, long long rows, int D, int lda, int ldb, float* out) {
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);     // one wave per row
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const T* pa = a + r * lda;
+    const T* pb = b + r * ldb;
+    constexpr int V = 16 / sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    float dot = 0.f, na = 0.f, nb = 0.f;
+    const bool vec = ((lda | ldb) % V) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+    const int dv = vec ? D / V : 0;
+    for (int i = lane; i < dv; i += 64) {
+        const vec_t x = *reinterpret_cast<const vec_t*>(pa + i * V), y = *reinterpret_cast<const vec_t*>(pb + i * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float fx = (float)x[j], fy = (float)y[j];
+            dot += fx * fy; na += fx * fx; nb += fy * fy;
+        }
+    }
+    for (int i = dv * V + lane; i < D; i += 64) {
+        const float fx = (float)pa[i], fy = (float)pb[i];
+        dot += fx * fy; na += fx * fx; nb += fy * fy;
+    }
+    dot = wave_sum(dot); na = wave_sum(na); nb = wave_sum(nb);
+    if (lane == 0) out[r] = dot / (sqrtf(na) * sqrtf(nb));     // x / |x| . y / |y| as the reference forms it: a zero row gives NaN there too
+}
+
+// ------------------------------------------------------------------------------------------- exact sum of squared byte differences
+constexpr int SQ_CHUNK = 256 * 16 * 8;         // bytes of one row per block: 8 x 16-byte loads per thread
+
+__global__ __launch_bounds__(256) void sq_diff_sum_u8_kernel(const unsigned char* a, const unsigned char* b, long long n, unsigned long long* out) {
+    const long long row = blockIdx.y;
+    const unsigned char* pa = a + row * n;
+    const unsigned char* pb = b + row * n;
+    const long long c0 = (long long)blockIdx.x * SQ_CHUNK, c1 = min(c0 + SQ_CHUNK, n);
+    unsigned acc = 0;                          // <= 128 bytes per thread * 65025 fits 32 bits
+    if (((((uintptr_t)pa) | ((uintptr_t)pb)) & 15) == 0) {
+        for (long long i = c0 + threadIdx.x * 16; i + 16 <= c1; i += 256 * 16) {
+            const uint4 x = *reinterpret_cast<const uint4*>(pa + i), y = *reinterpret_cast<const uint4*>(pb + i);
+            const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int s = 0; s < 32; s += 8) {
+                    const int d = (int)((xs[w] >> s) & 255u) - (int)((ys[w] >> s) & 255u);
+                    acc += (unsigned)(d * d);
+                }
+        }
+        const long long tail = c0 + ((c1 - c0) & ~15LL);       // SQ_CHUNK is a multiple of 16: only the row's last chunk has a tail
+        for (long long i = tail + threadIdx.x; i < c1; i += 256) {
+            const int d = (int)pa[i] - (int)pb[i];
+            acc += (unsigned)(d * d);
+        }
+    } else {
+        for (long long i = c0 + threadIdx.x; i < c1; i += 256) {      // 128 bytes per thread
+            const int d = (int)pa[i] - (int)pb[i];
+            acc += (unsigned)(d * d);
+        }
+    }
+    // 64 lanes * 128 * 65025 overflows 32 bits: widen before the reduction
+    unsigned long long s = acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out + row, part[0] + part[1] + part[2] + part[3]);
+}
+
+}  // namespace
+
+extern "C" int icd_clip_preprocess(const void* images, int32_t B, int32_t H, int32_t W, int32_t resized_h, int32_t resized_w, int32_t crop,
+                                   int32_t patch, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
+                                   const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps,
+                                   const float* mean, const float* stdv, void* tmp, void* out, int32_t ldo, void* stream) {
+    ICD_CHECK_ARG(images && tmp && out && mean && stdv, "icd_clip_preprocess: null pointer");
+    ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_clip_preprocess: null coefficient table");
+    ICD_CHECK_ARG(B > 0, "icd_clip_preprocess: B must be positive (got %d)", B);
+    ICD_CHECK_ARG(H > 0 && W > 0 && resized_h > 0 && resized_w > 0, "icd_clip_preprocess: sizes must be positive");
+    ICD_CHECK_ARG(patch > 0 && crop > 0 && crop % patch == 0 && crop % 4 == 0 && crop <= 1024 && patch <= 64,
+                  "icd_clip_preprocess: crop must be a multiple of the patch size and of 4, <= 1024");
+    ICD_CHECK_ARG(resized_h >= crop && resized_w >= crop, "icd_clip_preprocess: the resized image (%d x %d) is smaller than the crop %d",
+                  resized_h, resized_w, crop);
+    ICD_CHECK_ARG(ldo % 8 == 0 && ldo >= 3 * patch * patch, "icd_clip_preprocess: ldo must be a multiple of 8, >= 3 * patch^2");
+    ICD_CHECK_ARG(W <= 4096, "icd_clip_preprocess: image width %d exceeds 4096", W);
+    ICD_CHECK_ARG(((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out & 15) == 0,
+                  "icd_clip_preprocess: tmp must be 4-byte aligned, out 16-byte aligned");
+    ICD_CHECK_ARG((long long)patch * crop * 3 <= 65536, "icd_clip_preprocess: patch * crop * 3 = %lld bytes of LDS exceed 64 KiB",
+                  (long long)patch * crop * 3);
+    // the tables' row length follows from the sizes (Pillow: 2 * ceil(2 * max(in / out, 1)) + 1): a table built for other sizes is refused
+    auto taps = [](int in, int o) { const double s = (double)in / o; return (int)ceil(2.0 * (s > 1.0 ? s : 1.0)) * 2 + 1; };
+    ICD_CHECK_ARG(h_taps == taps(W, resized_w) && v_taps == taps(H, resized_h),
+                  "icd_clip_preprocess: tables do not match the sizes (taps %d / %d, expected %d / %d)", h_taps, v_taps, taps(W, resized_w),
+                  taps(H, resized_h));
+    for (int c = 0; c < 3; ++c) ICD_CHECK_ARG(stdv[c] > 0.f, "icd_clip_preprocess: std must be positive");
+    PreK p;
+    p.img = (const unsigned char*)images; p.tmp = (unsigned char*)tmp; p.out = (half_t*)out;
+    const int left = (resized_w - crop) / 2, top = (resized_h - crop) / 2;
+    p.hfirst = h_first + left; p.hcount = h_count + left; p.hcoef = h_coef + (long long)left * h_taps;
+    p.vfirst = v_first + top; p.vcount = v_count + top; p.vcoef = v_coef + (long long)top * v_taps;
+    p.B = B; p.H = H; p.W = W; p.S = crop; p.P = patch; p.G = crop / patch; p.ldo = ldo; p.hk = h_taps; p.vk = v_taps;
+    p.rows = (long long)B * H;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds_h = (size_t)HROWS * W * 3 + 32;
+    hipLaunchKernelGGL(clip_resample_h_kernel, dim3((unsigned)((p.rows + HROWS - 1) / HROWS)), dim3(256), lds_h, st, p);
+    ICD_CHECK_LAUNCH("icd_clip_preprocess (horizontal)");
+    hipLaunchKernelGGL(clip_resample_v_kernel, dim3((unsigned)(B * p.G)), dim3(256), (size_t)patch * crop * 3, st, p);
+    ICD_CHECK_LAUNCH("icd_clip_preprocess (vertical)");
+    return ICD_OK;
+}
+
+extern "C" int icd_cosine_rows(const void* a, const void* b, int64_t rows, int32_t D, int32_t lda, int32_t ldb, int32_t is_f32, float* out,
+                               void* stream) {
+    ICD_CHECK_ARG(a && b && out, "icd_cosine_rows: null pointer");
+    ICD_CHECK_ARG(rows > 0 && D > 0 && lda >= D && ldb >= D, "icd_cosine_rows: bad shape (rows %lld, D %d, lda %d, ldb %d)", (long long)rows, D,
+                  lda, ldb);
+    ICD_CHECK_ARG(is_f32 == 0 || is_f32 == 1, "icd_cosine_rows: is_f32 must be 0 or 1");
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (is_f32)
+        hipLaunchKernelGGL(cosine_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (long long)rows,
+                           D, lda, ldb, out);
+    else
+        hipLaunchKernelGGL(cosine_rows_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)stream, (const half_t*)a, (const half_t*)b,
+                           (long long)rows, D, lda, ldb, out);
+    ICD_CHECK_LAUNCH("icd_cosine_rows");
+    return ICD_OK;
+}
+
+extern "C" int icd_sq_diff_sum_u8(const void* a, const void* b, int64_t rows, int64_t n, uint64_t* out, void* stream) {
+    ICD_CHECK_ARG(a && b && out, "icd_sq_diff_sum_u8: null pointer");
+    ICD_CHECK_ARG(rows > 0 && rows <= 65535 && n > 0, "icd_sq_diff_sum_u8: rows must be in 1 .. 65535 and n positive");
+    ICD_CHECK_ARG(n <= (1LL << 40), "icd_sq_diff_sum_u8: n too large");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(out, 0, (size_t)rows * sizeof(uint64_t), st) != hipSuccess) {
+        icd_set_error("icd_sq_diff_sum_u8: hipMemsetAsync failed");
+        return ICD_ERR_HIP;
+    }
+    hipLaunchKernelGGL(sq_diff_sum_u8_kernel, dim3((unsigned)((n + SQ_CHUNK - 1) / SQ_CHUNK), (unsigned)rows), dim3(256), 0, st,
+                       (const unsigned char*)a, (const unsigned char*)b, (long long)n, (unsigned long long*)out);
+    ICD_CHECK_LAUNCH("icd_sq_diff_sum_u8");
+    return ICD_OK;
+}

@@ -60,6 +60,8 @@ def runner(model, prompt, controller, solver, is_cons_forward=False, num_inferen
     latents = trajectory[-1]
     if return_type == 'image':
         image = latent2image(model.vae, latents.to(model.vae.dtype))
+    elif return_type == 'uint8_device':                # the same bytes, left on the device (metrics.py scores them there)
+        image = latent2image(model.vae, latents.to(model.vae.dtype), on_device=True)
     else:
         image = latents
     return image, latent
@@ -310,12 +312,15 @@ class Generator:
     # ------------------------------------------------------------------ VAE / text plumbing (out of the hot path)
     @torch.no_grad()
     def latent2image(self, latents, return_type='np'):
+        """'np': the FIRST image as a uint8 HWC array (utils/generation.py); 'uint8_device': the whole batch, uint8 NHWC on the device."""
         latents = 1 / 0.18215 * latents.detach()
         image = self.model.vae.decode(latents.to(dtype=self.model.dtype))['sample']
         if return_type == 'np':
             image = (image / 2 + 0.5).clamp(0, 1)
             image = image.cpu().permute(0, 2, 3, 1).numpy()[0]
             image = (image * 255).astype(np.uint8)
+        elif return_type == 'uint8_device':
+            image = _to_uint8_device(image)
         return image
 
     @torch.no_grad()
@@ -447,8 +452,18 @@ class Generator:
 
 
 # ----------------------------------------------------------------------------------------------------------- misc utils
-def latent2image(vae, latents):
+def _to_uint8_device(image):
+    """decoded NCHW sample -> uint8 NHWC on its device: clamp, scale and truncate towards zero in the sample's own dtype, the values
+    `(image * 255).astype(np.uint8)` takes on the host (the same elementwise arithmetic; the values lie in [0, 255])."""
+    image = (image / 2 + 0.5).clamp(0, 1)
+    return (image.permute(0, 2, 3, 1) * 255).to(torch.uint8).contiguous()
+
+
+def latent2image(vae, latents, on_device=False):
+    """uint8 NHWC images: a numpy array, or with on_device=True a tensor that stays on the device."""
     image = vae.decode(1 / 0.18215 * latents)['sample']
+    if on_device:
+        return _to_uint8_device(image)
     image = (image / 2 + 0.5).clamp(0, 1)
     image = image.cpu().permute(0, 2, 3, 1).numpy()
     return (image * 255).astype(np.uint8)

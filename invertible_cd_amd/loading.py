@@ -112,6 +112,37 @@ def _build_text_encoders(comp, device, dtype, xl):
         comp["text_encoder_2"] = CLIPTextModel(OPENCLIP_BIGG, comp["text_encoder_2_state_dict"], True, device, dtype)
 
 
+def load_clip(path_or_state_dict, device="cuda", dtype=torch.float16, text_config=None, vision_config=None):
+    """The joint CLIP model of the edit-quality metrics (metrics.py) on the HIP kernels: a `transformers`-layout directory
+    (`config.json` + `model.safetensors`, e.g. a local copy of openai/clip-vit-large-patch14) or a state dict in that layout
+    (`text_model.*`, `vision_model.*`, `text_projection.weight`, `visual_projection.weight`).  Configurations default to ViT-L/14; a
+    directory's config.json overrides the fields it names."""
+    from .clip import CLIPModel, CLIPTextConfig, CLIPVisionConfig, CLIP_VIT_L, CLIP_VIT_L_VISION
+    tcfg, vcfg = text_config or CLIP_VIT_L, vision_config or CLIP_VIT_L_VISION
+    sd = path_or_state_dict
+    if isinstance(sd, (str, os.PathLike)):
+        import json
+        from safetensors.torch import load_file
+        root = os.fspath(sd)
+        weights = os.path.join(root, "model.safetensors")
+        if not os.path.exists(weights):
+            raise FileNotFoundError(f"load_clip: {weights} not found (want a transformers-layout directory)")
+        cfg_path = os.path.join(root, "config.json")
+        if os.path.exists(cfg_path):
+            with open(cfg_path) as f:
+                cfg = json.load(f)
+
+            def merged(base, section, cls):
+                d = dict(cfg.get(section) or {})
+                if "projection_dim" in cfg:
+                    d.setdefault("projection_dim", cfg["projection_dim"])
+                names = {f.name for f in dataclasses.fields(cls)}
+                return dataclasses.replace(base, **{k: v for k, v in d.items() if k in names})
+            tcfg, vcfg = merged(tcfg, "text_config", CLIPTextConfig), merged(vcfg, "vision_config", CLIPVisionConfig)
+        sd = load_file(weights)
+    return CLIPModel(tcfg, vcfg, sd, device, dtype)
+
+
 def load_models(model_id, device, reverse_checkpoint, forward_checkpoint, r=64, w_embed_dim=0, teacher_checkpoint=None,
                 dtype='fp32', components=None, unet_config=None):
     """SD1.5: (ldm_stable, reverse_cons_model, forward_cons_model).  `components` may supply real

@@ -593,3 +593,58 @@ def accumulate_multi(dst, src):
             assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float16 and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
             dp[t], sp[t], cn[t] = a.data_ptr(), b.data_ptr(), a.numel()
         _lib.check(lib.icd_accumulate_multi(dp, sp, cn, n, _stream()), "icd_accumulate_multi")
+
+
+# ------------------------------------------------------------------------------------------------ edit-quality metrics
+_RESAMPLE_DEV = {}
+
+
+def _resample_tables_dev(in_size, out_size, device):
+    """resample.resample_tables on the device (int32), cached per (sizes, device): uploaded once, read by every later call."""
+    key = (in_size, out_size, str(device))
+    if key not in _RESAMPLE_DEV:
+        from . import resample
+        _RESAMPLE_DEV[key] = tuple(torch.from_numpy(t.copy()).to(device).contiguous() for t in resample.resample_tables(in_size, out_size))
+    return _RESAMPLE_DEV[key]
+
+
+def clip_preprocess(images, size=224, crop=224, patch=14, mean=None, std=None):
+    """uint8 NHWC images [B, H, W, 3] on the device -> fp16 patch matrix [B * (crop / patch)^2, pad8(3 * patch^2)] of
+    transformers.CLIPImageProcessor (Pillow BICUBIC shortest-edge resize, centre crop, normalise), columns as patch_embedding.weight
+    flattens (icd_clip_preprocess)."""
+    from . import resample
+    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
+        "clip_preprocess: need a contiguous cuda uint8 [B, H, W, 3] tensor"
+    B, H, W, _ = images.shape
+    rh, rw, _, _ = resample.clip_geometry(H, W, size, crop)
+    hf, hc, hk = _resample_tables_dev(W, rw, images.device)
+    vf, vc, vk = _resample_tables_dev(H, rh, images.device)
+    g = crop // patch
+    ldo = (3 * patch * patch + 7) // 8 * 8
+    tmp = torch.empty((B * H, crop, 3), device=images.device, dtype=torch.uint8)
+    out = torch.empty((B * g * g, ldo), device=images.device, dtype=torch.float16)
+    m3 = (C.c_float * 3)(*(mean or resample.CLIP_MEAN))
+    s3 = (C.c_float * 3)(*(std or resample.CLIP_STD))
+    _lib.check(_lib.load().icd_clip_preprocess(_p(images), B, H, W, rh, rw, crop, patch, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf), _p(vc),
+                                               _p(vk), vk.shape[1], m3, s3, _p(tmp), _p(out), ldo, _stream()), "icd_clip_preprocess")
+    return out
+
+
+def cosine_rows(a, b):
+    """fp32 [N]: cosine of corresponding rows of a, b [N, D] (both fp16 or both fp32, row-major, unit inner stride)."""
+    assert a.is_cuda and b.is_cuda and a.dim() == 2 and a.shape == b.shape and a.dtype == b.dtype and a.dtype in (torch.float16, torch.float32)
+    assert a.stride(1) == 1 and b.stride(1) == 1, "cosine_rows: rows must be contiguous"
+    out = torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
+    _lib.check(_lib.load().icd_cosine_rows(_p(a), _p(b), a.shape[0], a.shape[1], a.stride(0), b.stride(0), int(a.dtype == torch.float32),
+                                           _p(out), _stream()), "icd_cosine_rows")
+    return out
+
+
+def sq_diff_sum_u8(a, b):
+    """int64 [N]: exact sum of squared differences of the uint8 rows a, b [N, ...]."""
+    assert a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.shape == b.shape and a.dim() >= 1
+    a, b = a.contiguous(), b.contiguous()
+    rows = a.shape[0]
+    out = torch.empty((rows,), device=a.device, dtype=torch.int64)          # the kernel writes uint64; the sums stay far below 2^63
+    _lib.check(_lib.load().icd_sq_diff_sum_u8(_p(a), _p(b), rows, a.numel() // rows, _p(out), _stream()), "icd_sq_diff_sum_u8")
+    return out

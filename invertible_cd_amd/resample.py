@@ -1,0 +1,99 @@
+"""Host side of the CLIP image preprocessing: Pillow's BICUBIC resample restated as integer coefficient tables.
+
+`PIL.Image.resize(size, BICUBIC)` is an antialiased two-pass separable resample (horizontal pass, then vertical): the cubic filter
+(a = -0.5) is stretched by the scale factor when shrinking, each output pixel's taps are normalised in double, rounded to fixed point
+with 22 fractional bits, and both passes accumulate in int32 and clip to uint8.  Once the tables exist the arithmetic is pure integer,
+so `icd_clip_preprocess` (csrc/metrics.hip) reproduces it bit for bit.  This module is numpy only: it builds the tables, states the
+shortest-edge / centre-crop geometry of `transformers.CLIPImageProcessor`, and carries a numpy emulation of the two passes (the CPU
+test's check of the tables against Pillow itself; the device kernel is checked against Pillow on the GPU).
+"""
+import functools
+import math
+
+import numpy as np
+
+PRECISION_BITS = 32 - 8 - 2                      # Pillow's fixed-point fraction: int32 accumulators, 8-bit samples, 2 bits of headroom
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def _bicubic(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return 0.0
+
+
+def tap_width(in_size, out_size):
+    """Row length of the coefficient table (Pillow's ksize): 2 * ceil(support) + 1 with support = 2 * max(in / out, 1)."""
+    return int(math.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+@functools.lru_cache(maxsize=64)
+def resample_tables(in_size, out_size):
+    """One axis of the resample: (first [out] int32, count [out] int32, coef [out, tap_width] int32, zero padded).
+
+    Output pixel i is clip8((sum_k coef[i, k] * in[first[i] + k] + 2^21) >> 22) over k < count[i]."""
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"resample_tables: sizes must be positive, got {in_size} -> {out_size}")
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = tap_width(in_size, out_size)
+    first = np.zeros(out_size, np.int32)
+    count = np.zeros(out_size, np.int32)
+    coef = np.zeros((out_size, ksize), np.int32)
+    ss = 1.0 / filterscale
+    for i in range(out_size):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = np.array([_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)], np.float64)
+        total = 0.0
+        for v in w:                               # Pillow sums in tap order; keep the order so the double result is the same
+            total += v
+        if total != 0.0:
+            w = w / total
+        k = np.where(w < 0, (-0.5 + w * (1 << PRECISION_BITS)).astype(np.int64), (0.5 + w * (1 << PRECISION_BITS)).astype(np.int64))
+        first[i], count[i] = xmin, xmax
+        coef[i, :xmax] = k                        # astype(int64) truncates towards zero, as the C cast does
+    for a in (first, count, coef):
+        a.setflags(write=False)
+    return first, count, coef
+
+
+def clip_geometry(height, width, size=224, crop=224):
+    """(resized_h, resized_w, top, left) of CLIPImageProcessor: shortest edge -> `size` (the longer one truncated), centre crop."""
+    if height <= 0 or width <= 0:
+        raise ValueError(f"clip_geometry: bad image size {height} x {width}")
+    short, long = (width, height) if width <= height else (height, width)
+    new_long = int(size * long / short)
+    rh, rw = (new_long, size) if width <= height else (size, new_long)
+    if rh < crop or rw < crop:
+        raise ValueError(f"clip_geometry: resized image {rh} x {rw} is smaller than the {crop} crop")
+    return rh, rw, (rh - crop) // 2, (rw - crop) // 2
+
+
+def _pass(img, tables, axis):
+    first, count, coef = tables
+    img = np.moveaxis(img, axis, 0).astype(np.int64)
+    out = np.empty((len(first),) + img.shape[1:], np.uint8)
+    for i in range(len(first)):
+        k = coef[i, :count[i]].astype(np.int64)
+        acc = np.tensordot(k, img[first[i]:first[i] + count[i]], axes=(0, 0)) + (1 << (PRECISION_BITS - 1))
+        out[i] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return np.moveaxis(out, 0, axis)
+
+
+def resize_emulated(img, out_h, out_w):
+    """numpy restatement of the two integer passes on a uint8 [H, W, C] image (what the device kernel computes)."""
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim == 3
+    h, w = img.shape[:2]
+    if out_w != w:                                # Pillow skips a pass whose size does not change
+        img = _pass(img, resample_tables(w, out_w), 1)
+    if out_h != h:
+        img = _pass(img, resample_tables(h, out_h), 0)
+    return img

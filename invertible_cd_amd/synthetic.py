@@ -209,3 +209,23 @@ class SyntheticVAE:
         im = torch.einsum("cl,blhw->bchw", self.dec.to(z.device), z.float())
         im = torch.nn.functional.interpolate(im, scale_factor=8.0, mode="nearest").to(z.dtype)
         return {"sample": im} if return_dict else (im,)
+
+
+def synthetic_clip_vision_state_dict(cfg, seed: int = 0, device="cpu", dtype=torch.float32, prefix="vision_model."):
+    """Seeded CLIP image-tower weights in the checkpoint key layout (clip.CLIPVisionConfig.state_dict_shapes)."""
+    sd = {}
+    for key, shape in cfg.state_dict_shapes().items():
+        g = _gen("clip_vision:" + key, seed, device)
+        if key.endswith(".bias"):
+            t = 0.05 * torch.randn(shape, generator=g, device=device)
+        elif "norm" in key:
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g, device=device)
+        elif key.endswith("patch_embedding.weight"):
+            t = torch.randn(shape, generator=g, device=device) * (shape[1] * shape[2] * shape[3]) ** -0.5
+        elif "embedding" in key:
+            t = 0.5 * torch.randn(shape, generator=g, device=device)
+        else:
+            gain = 0.5 if key.endswith(("out_proj.weight", "fc2.weight")) else 1.0
+            t = torch.randn(shape, generator=g, device=device) * (gain / shape[-1] ** 0.5)
+        sd[(prefix if key != "visual_projection.weight" else "") + key] = t.to(dtype)
+    return sd
