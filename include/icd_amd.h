@@ -544,6 +544,13 @@ int icd_clip_preprocess(const void* images, int32_t B, int32_t H, int32_t W, int
                         int32_t patch, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
                         const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps,
                         const float* mean, const float* stdv, void* tmp, void* out, int32_t ldo, void* stream);
+/* The embeddings of a ViT whose patch bias, class token and position table were folded into one fp32 table tok [1 + n, C] at load time
+ * (row 0: class token + its position; row 1 + p: position p + patch bias): out32[b, 0] = tok[0], out32[b, 1 + p] = acc[b * n + p] +
+ * tok[1 + p] with acc the patch GEMM's fp32 output [B * n, lda] (columns past C are not read), out16 = fp16(out32), both
+ * [B * (1 + n), C]: the fp16 residual stream and its fp32 twin start from one add and one rounding per element.  C % 8 == 0,
+ * lda % 4 == 0, lda >= C, all pointers 16-byte aligned.  One launch. */
+int icd_vit_tokens(const float* acc, int32_t lda, const float* tok, int32_t B, int32_t n, int32_t C, void* out16, float* out32,
+                   void* stream);
 /* out[r] = a[r] . b[r] / (|a[r]| |b[r]|) for row-major a, b [rows, D] (fp16, or fp32 when is_f32), fp32 accumulation, one wave per row. */
 int icd_cosine_rows(const void* a, const void* b, int64_t rows, int32_t D, int32_t lda, int32_t ldb, int32_t is_f32, float* out,
                     void* stream);

@@ -178,6 +178,7 @@ SIGNATURES = {
     "icd_unet_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "icd_clip_preprocess": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
                             + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "icd_vit_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icd_cosine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "icd_sq_diff_sum_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "icd_profile_enable": (C.c_int, [C.c_int32]),

@@ -1,6 +1,6 @@
-// Edit-quality metrics on the device: CLIP image preprocessing (Pillow's BICUBIC resample, bit for bit), row-wise cosine, and the exact
-// integer sum of squared differences behind PSNR.  All three are bandwidth kernels; the arithmetic is restated from Pillow's
-// documented behaviour (invertible_cd_amd/resample.py builds the coefficient tables).
+// Edit-quality metrics on the device: CLIP / DINOv2 image preprocessing (Pillow's BICUBIC resample, bit for bit), the token assembly of
+// a ViT's embeddings, row-wise cosine, and the exact integer sum of squared differences behind PSNR.  All are bandwidth kernels; the
+// resample arithmetic is restated from Pillow's documented behaviour (invertible_cd_amd/resample.py builds the coefficient tables).
 #include "common.h"
 
 namespace {
@@ -108,6 +108,34 @@ __global__ __launch_bounds__(256) void clip_resample_v_kernel(PreK p) {
         }
         *reinterpret_cast<f16x8*>(out + (long long)px_blk * p.ldo + c8) = v;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------- ViT token assembly
+// One thread owns 8 consecutive columns of one output row: two 16-byte loads from the token table (and from the patch GEMM's fp32
+// accumulator for a patch row), one fp32 add, two 16-byte fp32 stores and one 16-byte fp16 store.  Row offsets are 64-bit.
+__global__ __launch_bounds__(256) void vit_tokens_kernel(const float* acc, int lda, const float* tok, long long total, int T, int vpr,
+                                                         half_t* out16, float* out32) {
+    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (it >= total) return;
+    const long long row = it / vpr;                            // b * T + t
+    const int c8 = (int)(it - row * vpr) * 8;
+    const long long b = row / T;
+    const int t = (int)(row - b * T);
+    const int C = vpr * 8;
+    const float* pt = tok + (long long)t * C + c8;
+    f32x4 lo = *reinterpret_cast<const f32x4*>(pt), hi = *reinterpret_cast<const f32x4*>(pt + 4);
+    if (t > 0) {                                               // patch p = t - 1 of image b: row b * n + p of the accumulator
+        const float* pa = acc + (b * (T - 1) + (t - 1)) * (long long)lda + c8;
+        lo = *reinterpret_cast<const f32x4*>(pa) + lo;
+        hi = *reinterpret_cast<const f32x4*>(pa + 4) + hi;
+    }
+    float* po = out32 + row * C + c8;
+    *reinterpret_cast<f32x4*>(po) = lo;
+    *reinterpret_cast<f32x4*>(po + 4) = hi;
+    f16x8 h;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { h[j] = (half_t)lo[j]; h[4 + j] = (half_t)hi[j]; }
+    *reinterpret_cast<f16x8*>(out16 + row * C + c8) = h;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cosine of rows
@@ -221,6 +249,24 @@ extern "C" int icd_clip_preprocess(const void* images, int32_t B, int32_t H, int
     ICD_CHECK_LAUNCH("icd_clip_preprocess (horizontal)");
     hipLaunchKernelGGL(clip_resample_v_kernel, dim3((unsigned)(B * p.G)), dim3(256), (size_t)patch * crop * 3, st, p);
     ICD_CHECK_LAUNCH("icd_clip_preprocess (vertical)");
+    return ICD_OK;
+}
+
+extern "C" int icd_vit_tokens(const float* acc, int32_t lda, const float* tok, int32_t B, int32_t n, int32_t C, void* out16, float* out32,
+                              void* stream) {
+    ICD_CHECK_ARG(acc && tok && out16 && out32, "icd_vit_tokens: null pointer");
+    ICD_CHECK_ARG(B >= 1 && n >= 1, "icd_vit_tokens: B and n must be positive (got %d, %d)", B, n);
+    ICD_CHECK_ARG(C > 0 && C % 8 == 0, "icd_vit_tokens: C must be a positive multiple of 8 (got %d)", C);
+    ICD_CHECK_ARG(lda >= C && lda % 4 == 0, "icd_vit_tokens: lda must be a multiple of 4, >= C (got %d, C %d)", lda, C);
+    ICD_CHECK_ARG((((uintptr_t)acc | (uintptr_t)tok | (uintptr_t)out16 | (uintptr_t)out32) & 15) == 0,
+                  "icd_vit_tokens: pointers must be 16-byte aligned");
+    const int vpr = C / 8;
+    const long long total = (long long)B * ((long long)n + 1) * vpr;
+    const long long blocks = (total + 255) / 256;
+    ICD_CHECK_ARG(blocks <= 0x7fffffffLL, "icd_vit_tokens: %lld blocks exceed the grid limit", blocks);
+    hipLaunchKernelGGL(vit_tokens_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, lda, tok, total, n + 1, vpr,
+                       (half_t*)out16, out32);
+    ICD_CHECK_LAUNCH("icd_vit_tokens");
     return ICD_OK;
 }
 

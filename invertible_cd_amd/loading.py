@@ -143,6 +143,43 @@ def load_clip(path_or_state_dict, device="cuda", dtype=torch.float16, text_confi
     return CLIPModel(tcfg, vcfg, sd, device, dtype)
 
 
+def load_dinov2(path_or_state_dict, device="cuda", dtype=torch.float16, config=None):
+    """The DINOv2 encoder of the preservation metric (metrics.calc_dinov2_images_images) on the HIP kernels: a `transformers`-layout
+    directory (`config.json` + `model.safetensors` or `pytorch_model.bin`, optionally `preprocessor_config.json`, e.g. a local copy of
+    facebook/dinov2-base) or a state dict in that layout.  The configuration defaults to dinov2-base; a directory's config.json overrides
+    the fields it names, its preprocessor_config.json the resize and crop sizes."""
+    from .dinov2 import Dinov2Config, Dinov2Model, DINOV2_BASE
+    cfg = config or DINOV2_BASE
+    sd = path_or_state_dict
+    if isinstance(sd, (str, os.PathLike)):
+        import json
+        root = os.fspath(sd)
+        st, pt = os.path.join(root, "model.safetensors"), os.path.join(root, "pytorch_model.bin")
+        if not os.path.exists(st) and not os.path.exists(pt):
+            raise FileNotFoundError(f"load_dinov2: neither {st} nor {pt} found (want a transformers-layout directory)")
+        names = {f.name for f in dataclasses.fields(Dinov2Config)}
+        over = {}
+        cfg_path, pre_path = os.path.join(root, "config.json"), os.path.join(root, "preprocessor_config.json")
+        if os.path.exists(cfg_path):
+            with open(cfg_path) as f:
+                over.update({k: v for k, v in json.load(f).items() if k in names})
+        if os.path.exists(pre_path):
+            with open(pre_path) as f:
+                pre = json.load(f)
+            side = lambda v, key: v.get(key, v.get("height")) if isinstance(v, dict) else v
+            if pre.get("crop_size") is not None:
+                over["crop_size"] = int(side(pre["crop_size"], "height"))
+            if pre.get("size") is not None:
+                over["resize_shortest_edge"] = int(side(pre["size"], "shortest_edge"))
+        cfg = dataclasses.replace(cfg, **over)
+        if os.path.exists(st):
+            from safetensors.torch import load_file
+            sd = load_file(st)
+        else:
+            sd = torch.load(pt, map_location="cpu", weights_only=True)
+    return Dinov2Model(cfg, sd, device, dtype)
+
+
 def load_models(model_id, device, reverse_checkpoint, forward_checkpoint, r=64, w_embed_dim=0, teacher_checkpoint=None,
                 dtype='fp32', components=None, unet_config=None):
     """SD1.5: (ldm_stable, reverse_cons_model, forward_cons_model).  `components` may supply real

@@ -1,16 +1,18 @@
-"""Edit-quality metrics on the device (API mirror of the CLIP scores and PSNR of the reference's utils/metrics.py).
+"""Edit-quality metrics on the device (API mirror of the DINOv2 score, the CLIP scores and PSNR of the reference's utils/metrics.py).
 
+    calc_dinov2_images_images(images_1, images_2, device, batch_size=50, model=...)          utils/metrics.py:176-207
     calc_clip_score_images_images(images_1, images_2, device, batch_size=50, model=...)      utils/metrics.py:211-242
     calc_clip_score_images_prompts(images, prompts, device, batch_size=50, model=...)        utils/metrics.py:246-280
     calculate_psnr(images_1, images_2, device, batch_size=50)                                utils/metrics.py:295-308
 
 Names, argument order and return values are the reference's; `model=` is what the reference fetched from the hub on every call
-(`AutoModel.from_pretrained('openai/clip-vit-large-patch14')`): a clip.CLIPModel, e.g. from loading.load_clip.  Images may be PIL
+(`AutoModel.from_pretrained('openai/clip-vit-large-patch14')`: a clip.CLIPModel, e.g. from loading.load_clip;
+`AutoModel.from_pretrained('facebook/dinov2-base')`: a dinov2.Dinov2Model, e.g. from loading.load_dinov2).  Images may be PIL
 images, numpy uint8 HWC arrays, or a uint8 NHWC tensor on the device (generation.runner(..., return_type='uint8_device')), which is
 preprocessed (icd_clip_preprocess), embedded and scored (icd_cosine_rows) without a copy to the host.  A list may mix image sizes (each size
 is preprocessed as one batch); a tensor or array holds one size.  `prompts` are token ids [N, T]
-(as everywhere in this package) or strings together with `tokenizer=`.  ImageReward, LPIPS, DINOv2 and FID stay out: their packages
-and weights are not available.
+(as everywhere in this package) or strings together with `tokenizer=`.  ImageReward, LPIPS and FID stay out: their packages (and
+weights) are not available.
 """
 import math
 
@@ -20,9 +22,9 @@ import torch
 from .resample import resample_tables, clip_geometry, resize_emulated   # noqa: F401  (the host tables are part of this module's interface)
 
 
-def _need_model(model):
+def _need_model(model, what="a clip.CLIPModel, e.g. loading.load_clip(path)"):
     if model is None:
-        raise ValueError("metrics: pass model= (a clip.CLIPModel, e.g. loading.load_clip(path)); nothing is downloaded here")
+        raise ValueError(f"metrics: pass model= ({what}); nothing is downloaded here")
     return model
 
 
@@ -59,6 +61,21 @@ def _token_ids(prompts, tokenizer):
             raise ValueError("metrics: string prompts need tokenizer= (or pass token ids [N, T])")
         return tokenizer(list(prompts), padding=True, truncation=True, max_length=77, return_tensors="pt").input_ids
     return torch.as_tensor(prompts)
+
+
+@torch.no_grad()
+def calc_dinov2_images_images(images_1, images_2, device, batch_size=50, model=None):
+    """Cosine of the DINOv2 class-token embeddings of corresponding images -> CPU float tensor [N] (the reference's preservation_dinov2)."""
+    from . import ops
+    model = _need_model(model, "a dinov2.Dinov2Model, e.g. loading.load_dinov2(path)")
+    n = _count(images_2)
+    assert _count(images_1) == n
+    scores = torch.zeros(n)
+    for i in range(0, n, batch_size):
+        e1 = _image_features(model, images_1[i:i + batch_size])
+        e2 = _image_features(model, images_2[i:i + batch_size])
+        scores[i:i + batch_size] = ops.cosine_rows(e2, e1).cpu()
+    return scores
 
 
 @torch.no_grad()

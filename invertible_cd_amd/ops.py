@@ -630,6 +630,19 @@ def clip_preprocess(images, size=224, crop=224, patch=14, mean=None, std=None):
     return out
 
 
+def vit_tokens(acc, tok, B):
+    """Embeddings of a ViT from the patch GEMM's fp32 output acc [B * n, >= C] (a row-major matrix or a column slice of one) and the
+    folded fp32 token table tok [1 + n, C] (icd_vit_tokens) -> (fp16 [B * (1 + n), C], fp32 [B * (1 + n), C])."""
+    assert acc.is_cuda and acc.dtype == torch.float32 and acc.dim() == 2 and acc.stride(1) == 1, "vit_tokens: acc must be row-major cuda fp32"
+    assert tok.is_cuda and tok.dtype == torch.float32 and tok.dim() == 2 and tok.is_contiguous(), "vit_tokens: tok must be contiguous cuda fp32"
+    T, Cc = tok.shape
+    assert acc.shape[0] == B * (T - 1) and acc.shape[1] >= Cc, f"vit_tokens: acc {tuple(acc.shape)} does not fit B = {B}, tok {tuple(tok.shape)}"
+    out16 = torch.empty((B * T, Cc), device=acc.device, dtype=torch.float16)
+    out32 = torch.empty((B * T, Cc), device=acc.device, dtype=torch.float32)
+    _lib.check(_lib.load().icd_vit_tokens(_p(acc), acc.stride(0), _p(tok), B, T - 1, Cc, _p(out16), _p(out32), _stream()), "icd_vit_tokens")
+    return out16, out32
+
+
 def cosine_rows(a, b):
     """fp32 [N]: cosine of corresponding rows of a, b [N, D] (both fp16 or both fp32, row-major, unit inner stride)."""
     assert a.is_cuda and b.is_cuda and a.dim() == 2 and a.shape == b.shape and a.dtype == b.dtype and a.dtype in (torch.float16, torch.float32)

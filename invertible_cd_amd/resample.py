@@ -15,6 +15,8 @@ import numpy as np
 PRECISION_BITS = 32 - 8 - 2                      # Pillow's fixed-point fraction: int32 accumulators, 8-bit samples, 2 bits of headroom
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)            # transformers.BitImageProcessor with DINOv2's preprocessor_config.json
+IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 def _bicubic(x, a=-0.5):

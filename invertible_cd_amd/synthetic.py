@@ -229,3 +229,26 @@ def synthetic_clip_vision_state_dict(cfg, seed: int = 0, device="cpu", dtype=tor
             t = torch.randn(shape, generator=g, device=device) * (gain / shape[-1] ** 0.5)
         sd[(prefix if key != "visual_projection.weight" else "") + key] = t.to(dtype)
     return sd
+
+
+def synthetic_dinov2_state_dict(cfg, seed: int = 0, device="cpu", dtype=torch.float32):
+    """Seeded DINOv2 weights in the checkpoint key layout (dinov2.Dinov2Config.state_dict_shapes), statistics as the CLIP image tower's.
+    LayerScale's lambda1 is uniform in [0.25, 1] and the patch bias is not zero: a fold that went missing shows in the embeddings."""
+    sd = {}
+    for key, shape in cfg.state_dict_shapes().items():
+        g = _gen("dinov2:" + key, seed, device)
+        if key.endswith("lambda1"):
+            t = 0.25 + 0.75 * torch.rand(shape, generator=g, device=device)
+        elif key.endswith(".bias"):
+            t = 0.05 * torch.randn(shape, generator=g, device=device)
+        elif "norm" in key:
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g, device=device)
+        elif key.endswith("projection.weight"):
+            t = torch.randn(shape, generator=g, device=device) * (shape[1] * shape[2] * shape[3]) ** -0.5
+        elif key.startswith("embeddings."):
+            t = 0.5 * torch.randn(shape, generator=g, device=device)
+        else:
+            gain = 0.5 if key.endswith(("output.dense.weight", "fc2.weight")) else 1.0
+            t = torch.randn(shape, generator=g, device=device) * (gain / shape[-1] ** 0.5)
+        sd[key] = t.to(dtype)
+    return sd
