@@ -558,6 +558,34 @@ int icd_cosine_rows(const void* a, const void* b, int64_t rows, int32_t D, int32
 int icd_sq_diff_sum_u8(const void* a, const void* b, int64_t rows, int64_t n, uint64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * LPIPS (csrc/lpips.hip): the reference's third preservation figure (utils/metrics.py calculate_lpips, piq.LPIPS on a VGG16 feature
+ * stack).  The 3x3 convolutions are icd_gemm's; these are the launches around them.  No float atomics anywhere: every result is
+ * bit-reproducible and does not depend on a sample's position in the batch.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* np.array(img.resize((S, S))) / 255, normalised, on uint8 NHWC images [B, H, W, 3] (device; `images` may start at any byte): Pillow's
+ * BICUBIC resize stretches both axes to S independently (no crop), then out[(b * S + y) * S + x] = 8 fp16 channels: channel c < 3 is
+ * fp16((u / 255 - mean[c]) / stdv[c]) evaluated in fp32 in that order, channels 3 .. 7 are zero (the Cin = 8 layout of the first
+ * convolution).  Tables as for icd_clip_preprocess: h_* for W -> S, v_* for H -> S, int32 on the device, h_taps / v_taps the row length
+ * Pillow uses for these sizes; an axis that keeps its size comes out equal to the input bytes.  mean / stdv: 3 floats each on the HOST.
+ * tmp: uint8 [B * H * S * 3] scratch on the device, 4-byte aligned; out 16-byte aligned.  Limits: S % 4 == 0, W <= 4096.  Two launches. */
+int icd_image_resize_norm(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first, const int32_t* h_count,
+                          const int32_t* h_coef, int32_t h_taps, const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef,
+                          int32_t v_taps, const float* mean, const float* stdv, void* tmp, void* out, void* stream);
+/* out = max(x, 0) over n fp16 elements, in place (out == x) or not; n % 8 == 0, pointers 16-byte aligned. */
+int icd_relu(const void* x, int64_t n, void* out, void* stream);
+/* MaxPool2d(2), floor mode, on NHWC fp16 x [B, H, W, C] -> out [B, H / 2, W / 2, C] (a last odd row / column is dropped);
+ * relu = 1: out = max(0, max of the four).  C % 8 == 0, H, W >= 2, pointers 16-byte aligned, out != x. */
+int icd_maxpool2x2(const void* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, void* out, void* stream);
+/* One tap of the LPIPS head.  f: fp16 [2 B * HW, ldf], samples 0 .. B - 1 the first images, B .. 2 B - 1 the second (columns past C are
+ * not read); w fp32 [C].  out[b] (+)= 1 / HW * sum_p sum_c w[c] * (a[p, c] / (sqrt(sum_c a[p, c]^2) + 1e-10) - b[p, c] / (sqrt(sum_c
+ * b[p, c]^2) + 1e-10))^2, all in fp32, with ReLU applied to f on load when relu = 1; accumulate = 1 adds to out[b], 0 overwrites it.
+ * Fixed summation order (per pixel, per block, then over the blocks' partial sums in `workspace`, at least
+ * icd_lpips_layer_workspace_bytes(B, HW, C) bytes).  C % 8 == 0, ldf % 8 == 0, ldf >= C, f and w 16-byte aligned.  Two launches. */
+int icd_lpips_layer(const void* f, int32_t ldf, int32_t B, int32_t HW, int32_t C, const float* w, int32_t relu, int32_t accumulate,
+                    void* workspace, int64_t workspace_bytes, float* out, void* stream);
+int64_t icd_lpips_layer_workspace_bytes(int32_t B, int32_t HW, int32_t C);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-kernel-family timing of the executor's launches with HIP events recorded on the launch stream (bench.py's
  * roofline leg).  No reference counterpart (the reference has no timing code at all).
  * ---------------------------------------------------------------------------------------------------------- */

@@ -180,6 +180,30 @@ def load_dinov2(path_or_state_dict, device="cuda", dtype=torch.float16, config=N
     return Dinov2Model(cfg, sd, device, dtype)
 
 
+def load_lpips(vgg_path_or_state_dict, lin_path_or_list, device="cuda", config=None):
+    """The LPIPS model of metrics.calculate_lpips on the HIP kernels.  `vgg_path_or_state_dict`: a torchvision vgg16 state dict
+    (`features.<i>.weight / .bias`; `classifier.*` is ignored), or a `.pt` / `.pth` / `.safetensors` file of one.  `lin_path_or_list`: piq's
+    `lpips_weights.pt` (a list of five [1, C, 1, 1] tensors), or such a list.  Nothing is downloaded."""
+    from .lpips import Lpips, LPIPS_VGG16
+
+    def read(src):
+        if not isinstance(src, (str, os.PathLike)):
+            return src
+        path = os.fspath(src)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"load_lpips: {path} not found")
+        if path.endswith(".safetensors"):
+            from safetensors.torch import load_file
+            return load_file(path)
+        return torch.load(path, map_location="cpu", weights_only=True)
+    sd = read(vgg_path_or_state_dict)
+    sd = {k: v for k, v in sd.items() if k.startswith("features.")}
+    lin = read(lin_path_or_list)
+    if isinstance(lin, dict):                                   # a safetensors file of the list: keys "0" .. "4"
+        lin = [lin[k] for k in sorted(lin, key=lambda k: int(str(k).split(".")[0]))]
+    return Lpips(config or LPIPS_VGG16, sd, list(lin), device)
+
+
 def load_models(model_id, device, reverse_checkpoint, forward_checkpoint, r=64, w_embed_dim=0, teacher_checkpoint=None,
                 dtype='fp32', components=None, unet_config=None):
     """SD1.5: (ldm_stable, reverse_cons_model, forward_cons_model).  `components` may supply real

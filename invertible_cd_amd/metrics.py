@@ -1,20 +1,26 @@
-"""Edit-quality metrics on the device (API mirror of the DINOv2 score, the CLIP scores and PSNR of the reference's utils/metrics.py).
+"""Edit-quality metrics on the device (API mirror of the DINOv2 score, the CLIP scores, PSNR, LPIPS and the inversion report of the
+reference's utils/metrics.py).
 
     calc_dinov2_images_images(images_1, images_2, device, batch_size=50, model=...)          utils/metrics.py:176-207
     calc_clip_score_images_images(images_1, images_2, device, batch_size=50, model=...)      utils/metrics.py:211-242
     calc_clip_score_images_prompts(images, prompts, device, batch_size=50, model=...)        utils/metrics.py:246-280
     calculate_psnr(images_1, images_2, device, batch_size=50)                                utils/metrics.py:295-308
+    calculate_lpips(images_1, images_2, device, batch_size=50, model=...)
+    calc_inversion(path_to_dir, device, dinov2_model=..., lpips_model=...)
 
 Names, argument order and return values are the reference's; `model=` is what the reference fetched from the hub on every call
 (`AutoModel.from_pretrained('openai/clip-vit-large-patch14')`: a clip.CLIPModel, e.g. from loading.load_clip;
-`AutoModel.from_pretrained('facebook/dinov2-base')`: a dinov2.Dinov2Model, e.g. from loading.load_dinov2).  Images may be PIL
-images, numpy uint8 HWC arrays, or a uint8 NHWC tensor on the device (generation.runner(..., return_type='uint8_device')), which is
-preprocessed (icd_clip_preprocess), embedded and scored (icd_cosine_rows) without a copy to the host.  A list may mix image sizes (each size
+`AutoModel.from_pretrained('facebook/dinov2-base')`: a dinov2.Dinov2Model, e.g. from loading.load_dinov2; `piq.LPIPS()`: a lpips.Lpips,
+e.g. from loading.load_lpips).  Images may be PIL images, numpy uint8 HWC arrays, or a uint8 NHWC tensor on the device
+(generation.runner(..., return_type='uint8_device')), which is preprocessed (icd_clip_preprocess / icd_image_resize_norm), embedded
+and scored (icd_cosine_rows / icd_lpips_layer) without a copy to the host.  A list may mix image sizes (each size
 is preprocessed as one batch); a tensor or array holds one size.  `prompts` are token ids [N, T]
-(as everywhere in this package) or strings together with `tokenizer=`.  ImageReward, LPIPS and FID stay out: their packages (and
-weights) are not available.
+(as everywhere in this package) or strings together with `tokenizer=`.  LPIPS is computed from its definition (a VGG16 feature stack,
+lpips.py) rather than through `piq`; ImageReward and FID stay out: their packages (and weights) are not available.
 """
+import json
 import math
+import os
 
 import numpy as np
 import torch
@@ -145,3 +151,50 @@ def calculate_psnr(images_1, images_2, device, batch_size=50):
             return out
         psnr += out
     return psnr
+
+
+@torch.no_grad()
+def calculate_lpips(images_1, images_2, device, batch_size=50, model=None):
+    """LPIPS of corresponding images -> CPU float tensor [N] (the reference's piq.LPIPS(reduction='none') on the images resized to
+    224 x 224).  Only the scores cross to the host."""
+    model = _need_model(model, "a lpips.Lpips, e.g. loading.load_lpips(vgg16_path, lpips_weights_path)")
+    n = _count(images_2)
+    assert _count(images_1) == n
+    scores = torch.zeros(n)
+    for i in range(0, n, batch_size):
+        scores[i:i + batch_size] = model(images_1[i:i + batch_size], images_2[i:i + batch_size]).cpu()
+    return scores
+
+
+def _directory_images(path):
+    """Every file of `path`, in sorted name order, as a 512 x 512 PIL image (generation.load_512 + to_pil_images)."""
+    from .generation import load_512, to_pil_images
+    return [to_pil_images(load_512(os.path.join(path, name))) for name in sorted(os.listdir(path))]
+
+
+def calc_inversion(path_to_dir, device, dinov2_model=None, lpips_model=None):
+    """The inversion report: `path_to_dir`/generated_images against `path_to_dir`/real_images, scored with the DINOv2 cosine, PSNR and
+    LPIPS in batches of 16, written to `path_to_dir`/preservation_metrics_values.json under the reference's three keys
+    (preservation_dinov2, preservation_psnr, preservation_lpips), each value the str() of a list of numpy scalars as the reference
+    formats it.  Returns that dict.  The reference pairs the files in os.listdir order, which promises nothing about two directories
+    agreeing; here BOTH LISTINGS ARE SORTED, so the i-th name of one directory meets the i-th name of the other (files without a
+    partner are left out)."""
+    _need_model(dinov2_model, "dinov2_model=, a dinov2.Dinov2Model, e.g. loading.load_dinov2(path)")
+    _need_model(lpips_model, "lpips_model=, a lpips.Lpips, e.g. loading.load_lpips(vgg16_path, lpips_weights_path)")
+    generated = _directory_images(os.path.join(path_to_dir, "generated_images"))
+    real = _directory_images(os.path.join(path_to_dir, "real_images"))
+    n = min(len(generated), len(real))
+    generated, real = generated[:n], real[:n]
+    scores = {
+        "preservation_dinov2": calc_dinov2_images_images(generated, real, device, batch_size=16, model=dinov2_model),
+        "preservation_psnr": calculate_psnr(generated, real, device, batch_size=16),
+        "preservation_lpips": calculate_lpips(generated, real, device, batch_size=16, model=lpips_model),
+    }
+    report = {}
+    for key, values in scores.items():
+        values = np.atleast_1d(np.array(values))     # PSNR is a bare inf as soon as one pair is identical
+        print(f"{key}: mean {float(np.mean(values.astype(np.float64)))}")
+        report[key] = str(list(values))
+    with open(os.path.join(path_to_dir, "preservation_metrics_values.json"), "w") as fp:
+        json.dump(report, fp)
+    return report

@@ -661,3 +661,57 @@ def sq_diff_sum_u8(a, b):
     out = torch.empty((rows,), device=a.device, dtype=torch.int64)          # the kernel writes uint64; the sums stay far below 2^63
     _lib.check(_lib.load().icd_sq_diff_sum_u8(_p(a), _p(b), rows, a.numel() // rows, _p(out), _stream()), "icd_sq_diff_sum_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS
+def image_resize_norm(images, size, mean, std):
+    """uint8 NHWC images [B, H, W, 3] on the device -> fp16 [B * size * size, 8]: np.array(PIL.Image.resize((size, size))) / 255 (Pillow's
+    BICUBIC, both axes stretched, no crop), normalised, channels 3 .. 7 zero (icd_image_resize_norm)."""
+    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
+        "image_resize_norm: need a contiguous cuda uint8 [B, H, W, 3] tensor"
+    B, H, W, _ = images.shape
+    hf, hc, hk = _resample_tables_dev(W, size, images.device)
+    vf, vc, vk = _resample_tables_dev(H, size, images.device)
+    tmp = torch.empty((B * H, size, 3), device=images.device, dtype=torch.uint8)
+    out = torch.empty((B * size * size, 8), device=images.device, dtype=torch.float16)
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _lib.check(_lib.load().icd_image_resize_norm(_p(images), B, H, W, size, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf), _p(vc), _p(vk),
+                                                 vk.shape[1], m3, s3, _p(tmp), _p(out), _stream()), "icd_image_resize_norm")
+    return out
+
+
+def relu(x, inplace=False):
+    _chk16(x, "x")
+    out = x if inplace else torch.empty_like(x)
+    _lib.check(_lib.load().icd_relu(_p(x), x.numel(), _p(out), _stream()), "icd_relu")
+    return out
+
+
+def maxpool2x2(x, B, H, W, relu=False):
+    """MaxPool2d(2), floor mode, over NHWC fp16 x [B * H * W, C] -> [B * (H // 2) * (W // 2), C]; relu: max(0, .) of the result."""
+    _chk16(x, "x")
+    Cc = x.shape[-1]
+    assert x.numel() == B * H * W * Cc, f"maxpool2x2: x {tuple(x.shape)} is not [{B} * {H} * {W}, C]"
+    out = torch.empty((B * (H // 2) * (W // 2), Cc), device=x.device, dtype=torch.float16)
+    _lib.check(_lib.load().icd_maxpool2x2(_p(x), B, H, W, Cc, int(relu), _p(out), _stream()), "icd_maxpool2x2")
+    return out
+
+
+def lpips_layer(f, B, HW, w, out=None, relu=False, accumulate=False):
+    """One tap of the LPIPS head (icd_lpips_layer): f fp16 [2 B * HW, C] (a row-major matrix or a column slice of one), the first B
+    samples against the last B, w fp32 [C] -> out fp32 [B] (+)= the weighted spatial mean of the squared difference of the
+    channel-normalised features."""
+    _chk_rows(f, "f")
+    Cc = f.shape[1]
+    assert f.shape[0] == 2 * B * HW, f"lpips_layer: f {tuple(f.shape)} is not [2 * {B} * {HW}, C]"
+    assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == Cc, "lpips_layer: w must be contiguous cuda fp32 [C]"
+    if out is None:
+        assert not accumulate, "lpips_layer: accumulate needs out="
+        out = torch.empty((B,), device=f.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B
+    lib = _lib.load()
+    n = lib.icd_lpips_layer_workspace_bytes(B, HW, Cc)
+    ws = torch.empty((max(n, 4),), device=f.device, dtype=torch.uint8)
+    _lib.check(lib.icd_lpips_layer(_p(f), f.stride(0), B, HW, Cc, _p(w), int(relu), int(accumulate), _p(ws), n, _p(out), _stream()),
+               "icd_lpips_layer")
+    return out

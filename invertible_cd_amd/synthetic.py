@@ -252,3 +252,19 @@ def synthetic_dinov2_state_dict(cfg, seed: int = 0, device="cpu", dtype=torch.fl
             t = torch.randn(shape, generator=g, device=device) * (gain / shape[-1] ** 0.5)
         sd[key] = t.to(dtype)
     return sd
+
+
+def synthetic_lpips_state(cfg, seed: int = 0, device="cpu", dtype=torch.float32):
+    """(vgg_state_dict, lin_weights) of lpips.Lpips: seeded VGG16 feature weights in torchvision's key layout (conv weights N(0, 2 / (9 Cin)),
+    which keeps the ReLU stack's activations O(1) through all five blocks; biases 0.05 N(0, 1)) and five non-negative U(0, 1) tap
+    weights in piq's [1, C, 1, 1] shape."""
+    sd = {}
+    for key, shape in cfg.state_dict_shapes().items():
+        g = _gen("lpips:" + key, seed, device)
+        if key.endswith(".bias"):
+            t = 0.05 * torch.randn(shape, generator=g, device=device)
+        else:
+            t = torch.randn(shape, generator=g, device=device) * (2.0 / (9 * shape[1])) ** 0.5
+        sd[key] = t.to(dtype)
+    lin = [torch.rand((1, w, 1, 1), generator=_gen(f"lpips:lin{i}", seed, device), device=device).to(dtype) for i, w in enumerate(cfg.widths)]
+    return sd, lin

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Editing with the quality metrics on the device: G [source, edit] pairs edited in one U-Net batch, decoded and scored without a host copy.
 
-    python tools/edit_metrics_bench.py [--pairs 8] [--reps 3] [--no-host-route] [--dinov2]
+    python tools/edit_metrics_bench.py [--pairs 8] [--reps 3] [--no-host-route] [--dinov2] [--lpips]
 
 Workload: tools/edit_batch_bench.py's (full-size SD1.5 on synthetic weights, 4-step consistency inversion + 4-step reverse edit with the
 shipped editing settings, p2p.ControllerBatch), followed by the AutoencoderKL decode to uint8 images on the device
@@ -10,7 +10,8 @@ source image), editing CLIP score (edited image vs edit prompt), PSNR (metrics.p
 images/s, edited + scored images/s and the mean scores.  For scale it also times the route this replaces: images copied to the host,
 transformers' PIL image processor, the transformers CLIP model in fp16 on the GPU.  Device windows are event-timed with a warm-up; the
 host route is wall time around a synchronise (its work is on the host).  --dinov2 adds the driver's fourth device-side score,
-preservation_dinov2 (metrics.calc_dinov2_images_images, dinov2-base on seeded weights), to the scored set and times it on its own as well.
+preservation_dinov2 (metrics.calc_dinov2_images_images, dinov2-base on seeded weights), to the scored set and times it on its own as well; --lpips does the same for preservation_lpips (metrics.calculate_lpips, the VGG16 stack at
+full width on seeded weights).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,9 +22,10 @@ ap.add_argument("--pairs", type=int, default=8)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--no-host-route", action="store_true")
 ap.add_argument("--dinov2", action="store_true", help="also score preservation_dinov2 (dinov2-base on seeded weights)")
+ap.add_argument("--lpips", action="store_true", help="also score preservation_lpips (VGG16 LPIPS on seeded weights)")
 a = ap.parse_args()
 
-from invertible_cd_amd import build, clip, dinov2, generation, metrics, p2p, synthetic, unet, vae
+from invertible_cd_amd import build, clip, dinov2, generation, lpips, metrics, p2p, synthetic, unet, vae
 from invertible_cd_amd.pipelines import StableDiffusionPipeline
 from invertible_cd_amd.schedulers import DDIMScheduler
 from invertible_cd_amd.unet_config import SD15
@@ -41,6 +43,7 @@ clip_sd = synthetic.synthetic_clip_state_dict(clip.CLIP_VIT_L, True, seed=0)
 clip_sd.update(synthetic.synthetic_clip_vision_state_dict(clip.CLIP_VIT_L_VISION, seed=0))
 scorer = clip.CLIPModel(clip.CLIP_VIT_L, clip.CLIP_VIT_L_VISION, clip_sd)
 dino = dinov2.Dinov2Model(dinov2.DINOV2_BASE, synthetic.synthetic_dinov2_state_dict(dinov2.DINOV2_BASE, seed=0)) if a.dinov2 else None
+lp = lpips.Lpips(lpips.LPIPS_VGG16, *synthetic.synthetic_lpips_state(lpips.LPIPS_VGG16, seed=0)) if a.lpips else None
 g = torch.Generator().manual_seed(453645634 + G)
 img = torch.randn(G, 4, 64, 64, generator=g).to(dev)
 ctx_inv = torch.randn(2 * G, 77, 768, generator=g).to(dev, torch.float16)
@@ -72,7 +75,11 @@ def score(images):
     assert src.is_cuda and out.is_cuda
     res = (metrics.calc_clip_score_images_images(src, out, dev, model=scorer), metrics.calc_clip_score_images_prompts(out, ids, dev, model=scorer),
            metrics.calculate_psnr(src, out, dev))
-    return res + (metrics.calc_dinov2_images_images(src, out, dev, model=dino),) if a.dinov2 else res
+    if a.dinov2:
+        res += (metrics.calc_dinov2_images_images(src, out, dev, model=dino),)
+    if a.lpips:
+        res += (metrics.calculate_lpips(src, out, dev, model=lp),)
+    return res
 
 
 def timed(fn, reps):
@@ -92,18 +99,22 @@ t_edit, images = timed(edit, a.reps)
 t_both, scores = timed(lambda: score(edit()), a.reps)
 t_score, _ = timed(lambda: score(images), a.reps)
 pres, edsc, psnr = scores[:3]
-n_scores = "four" if a.dinov2 else "three"
+n_scores = ("three", "four", "five")[int(a.dinov2) + int(a.lpips)]
 print(f"edit (inversion + edit + decode)            {t_edit:9.1f} ms  {G / t_edit * 1e3:7.2f} edited images/s")
 print(f"edit + scores on the device                 {t_both:9.1f} ms  {G / t_both * 1e3:7.2f} edited + scored images/s "
       f"({t_both / t_edit:.3f} x the edit alone)")
 print(f"the {n_scores} scores alone ({2 * G} CLIP image + {G} text embeddings, {G} PSNR" + (f", {2 * G} DINOv2 embeddings" if a.dinov2 else "")
-      + f")  {t_score:9.1f} ms")
+      + (f", {G} LPIPS pairs" if a.lpips else "") + f")  {t_score:9.1f} ms")
 if a.dinov2:
     t_dino, _ = timed(lambda: metrics.calc_dinov2_images_images(images[0::P].contiguous(), images[1::P].contiguous(), dev, model=dino), a.reps)
     print(f"preservation_dinov2 alone ({2 * G} images: preprocessing at 256 / 224, dinov2-base, cosine)  {t_dino:9.1f} ms")
+if a.lpips:
+    t_lp, _ = timed(lambda: metrics.calculate_lpips(images[0::P].contiguous(), images[1::P].contiguous(), dev, model=lp), a.reps)
+    print(f"preservation_lpips alone ({G} pairs: ingest at 224, VGG16 on {2 * G} images, five distance taps)  {t_lp:9.1f} ms")
 mean = lambda v: float(torch.as_tensor(v, dtype=torch.float64).mean())
 print(f"mean scores (synthetic weights: plumbing, not quality): preservation_clip_score {mean(pres):.4f}  editing_clip_score {mean(edsc):.4f}  "
-      f"psnr {mean(psnr) if isinstance(psnr, list) else psnr:.3f} dB" + (f"  preservation_dinov2 {mean(scores[3]):.4f}" if a.dinov2 else ""))
+      f"psnr {mean(psnr) if isinstance(psnr, list) else psnr:.3f} dB" + (f"  preservation_dinov2 {mean(scores[3]):.4f}" if a.dinov2 else "")
+      + (f"  preservation_lpips {mean(scores[-1]):.4f}" if a.lpips else ""))
 
 if not a.no_host_route:
     import transformers
