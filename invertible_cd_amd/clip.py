@@ -10,8 +10,8 @@ Architecture (transformers CLIPTextModel / CLIPTextModelWithProjection; oracle/c
 token + position embeddings (`icd_embed_tokens`), N pre-LayerNorm blocks of causal multi-head self-attention (head dim 64;
 `icd_attention_fused_ex` with ICD_ATTN_CAUSAL, q/k from one fused biased GEMM, V^T from the transposing GEMM epilogue) and a
 biased MLP (`icd_gemm` -> `icd_activation` quick_gelu | gelu -> `icd_gemm` + residual), final LayerNorm, EOS pooling, optional
-bias-free projection.  The V bias is folded into the output projection's bias (softmax rows sum to one, also under the
-causal mask).  fp16 storage, fp32 accumulation.  Tokenizers need a vocabulary that is not available offline: callers pass
+bias-free projection.  The blocks, their weight preparation and the fp32 twin of the residual stream are encoder.py's, shared with the
+image tower below and with dinov2.py.  Tokenizers need a vocabulary that is not available offline: callers pass
 token ids (synthetic.SyntheticTokenizer produces ids of the right shape).
 
 The image tower (`CLIPVisionModelWithProjection`) and the joint `CLIPModel` serve the edit-quality metrics (metrics.py): what the
@@ -25,6 +25,34 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from .encoder import ModelOutput, check_state_dict, check_widths, full, half, prepare_block, run_blocks
+from .encoder import images_to_device   # noqa: F401  (its first home: still importable from here)
+
+TextEncoderOutput = ModelOutput           # likewise
+
+
+def _block_shapes(C, I, layers):
+    """keys -> shapes of the encoder layers, which the two towers name alike"""
+    out = {}
+    for i in range(layers):
+        p = f"encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            out[p + f"self_attn.{n}.weight"] = (C, C); out[p + f"self_attn.{n}.bias"] = (C,)
+        for n in ("layer_norm1", "layer_norm2"):
+            out[p + n + ".weight"] = (C,); out[p + n + ".bias"] = (C,)
+        out[p + "mlp.fc1.weight"] = (I, C); out[p + "mlp.fc1.bias"] = (I,)
+        out[p + "mlp.fc2.weight"] = (C, I); out[p + "mlp.fc2.bias"] = (C,)
+    return out
+
+
+def _block_names(p):
+    a = p + "self_attn."
+    return {"q": a + "q_proj", "k": a + "k_proj", "v": a + "v_proj", "out": a + "out_proj", "norm1": p + "layer_norm1",
+            "norm2": p + "layer_norm2", "fc1": p + "mlp.fc1", "fc2": p + "mlp.fc2"}
+
+
+def _strip(sd, prefix):
+    return {(k[len(prefix):] if k.startswith(prefix) else k): v for k, v in sd.items()}
 
 
 @dataclass(frozen=True)
@@ -48,14 +76,7 @@ class CLIPTextConfig:
     def state_dict_shapes(self, with_projection=False):
         C, I, V, T = self.hidden_size, self.intermediate_size, self.vocab_size, self.max_position_embeddings
         out = {"embeddings.token_embedding.weight": (V, C), "embeddings.position_embedding.weight": (T, C)}
-        for i in range(self.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                out[p + f"self_attn.{n}.weight"] = (C, C); out[p + f"self_attn.{n}.bias"] = (C,)
-            for n in ("layer_norm1", "layer_norm2"):
-                out[p + n + ".weight"] = (C,); out[p + n + ".bias"] = (C,)
-            out[p + "mlp.fc1.weight"] = (I, C); out[p + "mlp.fc1.bias"] = (I,)
-            out[p + "mlp.fc2.weight"] = (C, I); out[p + "mlp.fc2.bias"] = (C,)
+        out.update(_block_shapes(C, I, self.num_hidden_layers))
         out["final_layer_norm.weight"] = (C,); out["final_layer_norm.bias"] = (C,)
         if with_projection:
             out["text_projection.weight"] = (self.projection_dim, C)
@@ -65,60 +86,25 @@ class CLIPTextConfig:
 CLIP_VIT_L = CLIPTextConfig()                                                        # SD1.5 / SDXL text_encoder
 OPENCLIP_BIGG = CLIPTextConfig(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
                                hidden_act="gelu", projection_dim=1280)               # SDXL text_encoder_2 (with projection)
-_ACT = {"quick_gelu": ops.ACT_QUICK_GELU, "gelu": ops.ACT_GELU}
-
-
-class TextEncoderOutput(tuple):
-    """Indexable like the transformers ModelOutput the reference indexes ([0]) with the attributes it reads."""
-
-    def __new__(cls, first, **fields):
-        self = super().__new__(cls, (first,) + tuple(v for v in fields.values() if v is not None))
-        self.__dict__.update(fields)
-        return self
-
-
-def _canon(sd):
-    return {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in sd.items()}
 
 
 class CLIPTextModel:
     def __init__(self, cfg: CLIPTextConfig, state_dict, with_projection=False, device="cuda", dtype=torch.float16):
-        if cfg.hidden_size % cfg.num_attention_heads or cfg.hidden_size // cfg.num_attention_heads > 160 \
-                or (cfg.hidden_size // cfg.num_attention_heads) % 8 or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
-            raise ValueError("CLIPTextModel: head dim must be a multiple of 8 and <= 160, widths multiples of 8")
-        if cfg.hidden_act not in _ACT:
-            raise ValueError(f"CLIPTextModel: unsupported hidden_act {cfg.hidden_act!r}")
+        check_widths("CLIPTextModel", cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size, cfg.hidden_act)
         self.cfg, self.with_projection = cfg, with_projection
         self.device, self.dtype = torch.device(device), dtype
         self.config = SimpleNamespace(**cfg.to_dict())
-        sd = _canon(state_dict)
-        want = cfg.state_dict_shapes(with_projection)
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"CLIP text state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for k, shp in want.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {tuple(shp)}, got {tuple(sd[k].shape)}")
+        sd = _strip(state_dict, "text_model.")
+        check_state_dict(sd, cfg.state_dict_shapes(with_projection), "CLIP text")
         f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
-        half = lambda t: t.to(device=device, dtype=torch.float16).contiguous()
-        full = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
-        w = {"tok": half(f32("embeddings.token_embedding.weight")), "pos": half(f32("embeddings.position_embedding.weight"))}
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            a = p + "self_attn."
-            w[p + "qk.w"] = half(torch.cat([f32(a + "q_proj.weight"), f32(a + "k_proj.weight")]))
-            w[p + "qk.b"] = full(torch.cat([f32(a + "q_proj.bias"), f32(a + "k_proj.bias")]))
-            w[p + "v.w"] = half(f32(a + "v_proj.weight"))
-            wo = f32(a + "out_proj.weight")
-            w[p + "o.w"] = half(wo)
-            w[p + "o.b"] = full(wo @ f32(a + "v_proj.bias") + f32(a + "out_proj.bias"))
-            for n in ("layer_norm1", "layer_norm2"):
-                w[p + n + ".w"], w[p + n + ".b"] = full(f32(p + n + ".weight")), full(f32(p + n + ".bias"))
-            for n in ("fc1", "fc2"):
-                w[p + n + ".w"], w[p + n + ".b"] = half(f32(p + f"mlp.{n}.weight")), full(f32(p + f"mlp.{n}.bias"))
-        w["ln_f.w"], w["ln_f.b"] = full(f32("final_layer_norm.weight")), full(f32("final_layer_norm.bias"))
+        w = {"tok": half(f32("embeddings.token_embedding.weight"), device), "pos": half(f32("embeddings.position_embedding.weight"), device)}
+        self.blocks = [f"encoder.layers.{i}." for i in range(cfg.num_hidden_layers)]
+        for p in self.blocks:
+            # the V bias is folded in fp32 here; float64 (as in the image tower) is sounder, but moves the text embeddings in the last bit
+            w.update((p + k, t) for k, t in prepare_block(f32, _block_names(p), device, fold_dtype=torch.float32).items())
+        w["ln_f.w"], w["ln_f.b"] = full(f32("final_layer_norm.weight"), device), full(f32("final_layer_norm.bias"), device)
         if with_projection:
-            w["proj.w"] = half(f32("text_projection.weight"))
+            w["proj.w"] = half(f32("text_projection.weight"), device)
         self.w = w
 
     def to(self, *args, **kw):
@@ -139,29 +125,11 @@ class CLIPTextModel:
         if int(ids.min()) < 0 or int(ids.max()) >= cfg.vocab_size:
             raise IndexError("CLIPTextModel: token id out of range")
         B, T = ids.shape
-        C, H = cfg.hidden_size, cfg.num_attention_heads
-        d, ld = C // H, (T + 7) // 8 * 8
+        C = cfg.hidden_size
         x = ops.embed_tokens(ids, w["tok"], w["pos"])
         hs = [x]
-        # Round 6: the residual stream keeps an fp32 twin (icd_gemm_desc.out_f32 + an fp32 `resid`): the 2 x num_hidden_layers adds x <- x + f(x)
-        # accumulate in fp32, the fp16 copy is what LayerNorm and the returned hidden states read (ViT-L 1.07e-3 -> < 1e-3 against transformers;
-        # the text encoders run once per prompt, outside every timed loop)
-        x32 = None
-
-        def add(f, wk, bk, x, x32):
-            n32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-            return ops.gemm(f, w[wk], w[bk], resid=x if x32 is None else x32, out32=n32), n32
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            h = ops.layernorm(x, w[p + "layer_norm1.w"], w[p + "layer_norm1.b"], cfg.layer_norm_eps)
-            qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"])
-            vt = ops.project_vt(h, w[p + "v.w"], B, T, ld)
-            o = ops.attention_fused(qk[:, :C], qk[:, C:], vt, B, H, T, T, d, d ** -0.5, causal=True)
-            x, x32 = add(o, p + "o.w", p + "o.b", x, x32)
-            h = ops.layernorm(x, w[p + "layer_norm2.w"], w[p + "layer_norm2.b"], cfg.layer_norm_eps)
-            f = ops.activation(ops.gemm(h, w[p + "fc1.w"], w[p + "fc1.b"]), _ACT[cfg.hidden_act])
-            x, x32 = add(f, p + "fc2.w", p + "fc2.b", x, x32)
-            hs.append(x)
+        # the text encoders run once per prompt, outside every timed loop: the fp32 twin of the residual stream costs nothing that is measured
+        x, _ = run_blocks(w, self.blocks, x, None, B, T, cfg.num_attention_heads, cfg.layer_norm_eps, cfg.hidden_act, True, hs)
         last = ops.layernorm(x, w["ln_f.w"], w["ln_f.b"], cfg.layer_norm_eps).reshape(B, T, C)
         if cfg.eos_token_id == 2:                               # transformers: legacy configs pool at argmax(input_ids)
             eos = ids.argmax(dim=-1)
@@ -172,8 +140,8 @@ class CLIPTextModel:
         hidden = tuple(cast(h.reshape(B, T, C)) for h in hs) if output_hidden_states else None
         if self.with_projection:
             embeds = ops.gemm(pooled, w["proj.w"])
-            return TextEncoderOutput(cast(embeds), text_embeds=cast(embeds), last_hidden_state=cast(last), hidden_states=hidden)
-        return TextEncoderOutput(cast(last), last_hidden_state=cast(last), pooler_output=cast(pooled), hidden_states=hidden)
+            return ModelOutput(cast(embeds), text_embeds=cast(embeds), last_hidden_state=cast(last), hidden_states=hidden)
+        return ModelOutput(cast(last), last_hidden_state=cast(last), pooler_output=cast(pooled), hidden_states=hidden)
 
 
 # ------------------------------------------------------------------------------------------------------------ image tower
@@ -203,14 +171,7 @@ class CLIPVisionConfig:
         out = {"embeddings.class_embedding": (C,), "embeddings.patch_embedding.weight": (C, self.num_channels, P, P),
                "embeddings.position_embedding.weight": (self.num_positions, C),
                "pre_layrnorm.weight": (C,), "pre_layrnorm.bias": (C,)}
-        for i in range(self.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                out[p + f"self_attn.{n}.weight"] = (C, C); out[p + f"self_attn.{n}.bias"] = (C,)
-            for n in ("layer_norm1", "layer_norm2"):
-                out[p + n + ".weight"] = (C,); out[p + n + ".bias"] = (C,)
-            out[p + "mlp.fc1.weight"] = (I, C); out[p + "mlp.fc1.bias"] = (I,)
-            out[p + "mlp.fc2.weight"] = (C, I); out[p + "mlp.fc2.bias"] = (C,)
+        out.update(_block_shapes(C, I, self.num_hidden_layers))
         out["post_layernorm.weight"] = (C,); out["post_layernorm.bias"] = (C,)
         out["visual_projection.weight"] = (self.projection_dim, C)
         return out
@@ -219,82 +180,30 @@ class CLIPVisionConfig:
 CLIP_VIT_L_VISION = CLIPVisionConfig()                                               # openai/clip-vit-large-patch14
 
 
-def _canon_vision(sd):
-    return {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in sd.items()}
-
-
-def images_to_device(images, device):
-    """PIL images / numpy uint8 HWC arrays (one size) / a uint8 NHWC tensor -> contiguous uint8 [B, H, W, 3] on `device`.  A tensor that
-    already lives there is returned as it is: nothing is copied to the host."""
-    import numpy as np
-    if isinstance(images, torch.Tensor):
-        t = images
-    else:
-        if not isinstance(images, (list, tuple)):
-            images = [images]
-        arrs = []
-        for im in images:
-            if isinstance(im, torch.Tensor):
-                im = im.cpu().numpy()
-            elif not isinstance(im, np.ndarray):
-                im = np.array(im.convert("RGB"))                # PIL: do_convert_rgb of the processor
-            arrs.append(im)
-        if len({a.shape for a in arrs}) != 1:
-            raise ValueError("images_to_device: images of several sizes; pass them in groups of one size")
-        t = torch.from_numpy(np.stack(arrs))
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
-        raise ValueError(f"images must be uint8 [B, H, W, 3], got {t.dtype} {tuple(t.shape)}")
-    return t.to(device).contiguous()
-
-
 class CLIPVisionModelWithProjection:
     def __init__(self, cfg: CLIPVisionConfig, state_dict, device="cuda", dtype=torch.float16):
-        d = cfg.hidden_size // max(cfg.num_attention_heads, 1)
-        if cfg.hidden_size % cfg.num_attention_heads or d > 160 or d % 8 or cfg.hidden_size % 8 or cfg.intermediate_size % 8 \
-                or cfg.projection_dim % 8:
-            raise ValueError("CLIPVisionModel: head dim must be a multiple of 8 and <= 160, widths multiples of 8")
-        if cfg.hidden_act not in _ACT:
-            raise ValueError(f"CLIPVisionModel: unsupported hidden_act {cfg.hidden_act!r}")
+        check_widths("CLIPVisionModel", cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size, cfg.hidden_act,
+                     extra=(cfg.projection_dim,))
         if cfg.num_channels != 3 or cfg.image_size % cfg.patch_size or cfg.image_size % 4:
             raise ValueError("CLIPVisionModel: 3 channels, image size a multiple of the patch size and of 4")
         self.cfg = cfg
         self.device, self.dtype = torch.device(device), dtype
         self.config = SimpleNamespace(**cfg.to_dict())
-        sd = _canon_vision(state_dict)
-        want = cfg.state_dict_shapes()
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"CLIP vision state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for k, shp in want.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {tuple(shp)}, got {tuple(sd[k].shape)}")
+        sd = _strip(state_dict, "vision_model.")
+        check_state_dict(sd, cfg.state_dict_shapes(), "CLIP vision")
         f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
-        half = lambda t: t.to(device=device, dtype=torch.float16).contiguous()
-        full = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
         C = cfg.hidden_size
         kp = 3 * cfg.patch_size ** 2
         wp = torch.zeros((C, (kp + 7) // 8 * 8))                 # icd_gemm needs K % 8 == 0: pad columns are zero here and in the patch matrix
         wp[:, :kp] = f32("embeddings.patch_embedding.weight").reshape(C, kp)
         pos = f32("embeddings.position_embedding.weight")
-        w = {"patch.w": half(wp), "pos": half(pos[1:]), "cls": half(f32("embeddings.class_embedding") + pos[0])}
-        w["ln_pre.w"], w["ln_pre.b"] = full(f32("pre_layrnorm.weight")), full(f32("pre_layrnorm.bias"))
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            a = p + "self_attn."
-            w[p + "qk.w"] = half(torch.cat([f32(a + "q_proj.weight"), f32(a + "k_proj.weight")]))
-            w[p + "qk.b"] = full(torch.cat([f32(a + "q_proj.bias"), f32(a + "k_proj.bias")]))
-            w[p + "v.w"] = half(f32(a + "v_proj.weight"))
-            wo = f32(a + "out_proj.weight")
-            w[p + "o.w"] = half(wo)
-            # softmax rows sum to one: the V bias leaves through the output bias.  Folded in float64 and rounded once, so that the prepared
-            # weights do not depend on which fp32 mat-vec path the host library takes for this tensor's alignment
-            w[p + "o.b"] = full((wo.double() @ f32(a + "v_proj.bias").double() + f32(a + "out_proj.bias").double()).float())
-            for n in ("layer_norm1", "layer_norm2"):
-                w[p + n + ".w"], w[p + n + ".b"] = full(f32(p + n + ".weight")), full(f32(p + n + ".bias"))
-            for n in ("fc1", "fc2"):
-                w[p + n + ".w"], w[p + n + ".b"] = half(f32(p + f"mlp.{n}.weight")), full(f32(p + f"mlp.{n}.bias"))
-        w["ln_post.w"], w["ln_post.b"] = full(f32("post_layernorm.weight")), full(f32("post_layernorm.bias"))
-        w["proj.w"] = half(f32("visual_projection.weight"))
+        w = {"patch.w": half(wp, device), "pos": half(pos[1:], device), "cls": half(f32("embeddings.class_embedding") + pos[0], device)}
+        w["ln_pre.w"], w["ln_pre.b"] = full(f32("pre_layrnorm.weight"), device), full(f32("pre_layrnorm.bias"), device)
+        self.blocks = [f"encoder.layers.{i}." for i in range(cfg.num_hidden_layers)]
+        for p in self.blocks:
+            w.update((p + k, t) for k, t in prepare_block(f32, _block_names(p), device).items())
+        w["ln_post.w"], w["ln_post.b"] = full(f32("post_layernorm.weight"), device), full(f32("post_layernorm.bias"), device)
+        w["proj.w"] = half(f32("visual_projection.weight"), device)
         self.w = w
 
     def eval(self):
@@ -314,7 +223,6 @@ class CLIPVisionModelWithProjection:
         if patches.dim() != 2 or patches.shape[0] % n or patches.shape[1] != w["patch.w"].shape[1]:
             raise ValueError(f"CLIPVisionModel: patch matrix must be [B * {n}, {w['patch.w'].shape[1]}], got {tuple(patches.shape)}")
         B = patches.shape[0] // n
-        d, ld = C // H, (T + 7) // 8 * 8
         # embeddings: patch GEMM (+ position rows as its residual), the class token (+ its position) in front
         pe = ops.gemm(patches, w["patch.w"], resid=w["pos"].repeat(B, 1))
         e = torch.empty((B, T, C), device=self.device, dtype=torch.float16)
@@ -322,22 +230,7 @@ class CLIPVisionModelWithProjection:
         e[:, 1:] = pe.reshape(B, n, C)
         x = ops.layernorm(e.reshape(B * T, C), w["ln_pre.w"], w["ln_pre.b"], cfg.layer_norm_eps)
         hs = [x]
-        x32 = None                                              # fp32 twin of the residual stream, as in the text tower
-
-        def add(f, wk, bk, x, x32):
-            n32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-            return ops.gemm(f, w[wk], w[bk], resid=x if x32 is None else x32, out32=n32), n32
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}."
-            h = ops.layernorm(x, w[p + "layer_norm1.w"], w[p + "layer_norm1.b"], cfg.layer_norm_eps)
-            qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"])
-            vt = ops.project_vt(h, w[p + "v.w"], B, T, ld)
-            o = ops.attention_fused(qk[:, :C], qk[:, C:], vt, B, H, T, T, d, d ** -0.5, causal=False)
-            x, x32 = add(o, p + "o.w", p + "o.b", x, x32)
-            h = ops.layernorm(x, w[p + "layer_norm2.w"], w[p + "layer_norm2.b"], cfg.layer_norm_eps)
-            f = ops.activation(ops.gemm(h, w[p + "fc1.w"], w[p + "fc1.b"]), _ACT[cfg.hidden_act])
-            x, x32 = add(f, p + "fc2.w", p + "fc2.b", x, x32)
-            hs.append(x)
+        x, _ = run_blocks(w, self.blocks, x, None, B, T, H, cfg.layer_norm_eps, cfg.hidden_act, False, hs)
         tok0 = x.reshape(B, T, C)[:, 0].contiguous()           # only the class token is pooled
         pooled = ops.layernorm(tok0, w["ln_post.w"], w["ln_post.b"], cfg.layer_norm_eps)
         embeds = ops.gemm(pooled, w["proj.w"], out_f32=True)
@@ -348,8 +241,8 @@ class CLIPVisionModelWithProjection:
     def __call__(self, images, output_hidden_states=False):
         out = self.forward_patches(self.preprocess(images), output_hidden_states)
         if output_hidden_states:
-            return TextEncoderOutput(out[0], image_embeds=out[0], hidden_states=out[1])
-        return TextEncoderOutput(out, image_embeds=out)
+            return ModelOutput(out[0], image_embeds=out[0], hidden_states=out[1])
+        return ModelOutput(out, image_embeds=out)
 
 
 class CLIPModel:

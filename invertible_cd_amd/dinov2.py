@@ -11,12 +11,14 @@ the start of the residual stream.
 
 Everything that does not depend on the image is folded on the host, once, at load time:
   * LayerScale: lambda1 of layer_scale1 scales the rows and the bias of attention.output.dense (the V bias leaves through that bias, as in
-    clip.py), lambda1 of layer_scale2 those of mlp.fc2 - in float64, rounded to the storage type afterwards.  No LayerScale pass runs.
+    clip.py), lambda1 of layer_scale2 those of mlp.fc2 - in float64, rounded to the storage type afterwards (encoder.fold_output).  No
+    LayerScale pass runs.
   * the position table is resized to (crop_size / patch_size)^2 by upstream's own `torch.nn.functional.interpolate` call (fp32, bicubic,
     align_corners=False), so the table is upstream's bit for bit; nothing is interpolated when the grids agree.
   * one fp32 token table tok [1 + n, C]: row 0 = cls_token + position 0, row 1 + p = position p + patch bias.
 On the device: `icd_clip_preprocess` at resize 256 / crop 224 with the ImageNet constants (transformers.BitImageProcessor), the patch
-GEMM with fp32 output, `icd_vit_tokens` (adds the table, writes the fp16 stream and its fp32 twin), then the operators of the CLIP towers.
+GEMM with fp32 output, `icd_vit_tokens` (adds the table, writes the fp16 stream and its fp32 twin), then the blocks of encoder.py, which
+the CLIP towers run too.
 """
 from dataclasses import dataclass, asdict
 from types import SimpleNamespace
@@ -24,7 +26,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .clip import TextEncoderOutput, _ACT, images_to_device
+from .encoder import ModelOutput, check_state_dict, check_widths, fold_output, full, half, images_to_device, prepare_block, run_blocks
 from .resample import IMAGENET_MEAN, IMAGENET_STD
 
 
@@ -92,12 +94,8 @@ def _canon(sd):
 
 
 def fold_layer_scale(weight, bias, lam, v_bias=None):
-    """float64 (W', b') with W' x + b' = lam * (W (x + v_bias) + b): LayerScale (and, for the attention output, the V bias that softmax
-    rows summing to one carry through unchanged) folded into the Linear in front of it."""
-    w, b, l = weight.double(), bias.double(), lam.double()
-    if v_bias is not None:
-        b = w @ v_bias.double() + b
-    return l[:, None] * w, l * b
+    """float64 (W', b') with W' x + b' = lam * (W (x + v_bias) + b): encoder.fold_output under the name and argument order it had here."""
+    return fold_output(weight, bias, v_bias, lam)
 
 
 def position_table(pos, grid):
@@ -119,11 +117,7 @@ class Dinov2Model:
     def __init__(self, cfg: Dinov2Config, state_dict, device="cuda", dtype=torch.float16):
         if cfg.use_swiglu_ffn:
             raise ValueError("Dinov2Model: use_swiglu_ffn (the giant model's feed-forward) is not supported")
-        d = cfg.hidden_size // max(cfg.num_attention_heads, 1)
-        if cfg.hidden_size % cfg.num_attention_heads or d > 160 or d % 8 or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
-            raise ValueError("Dinov2Model: head dim must be a multiple of 8 and <= 160, widths multiples of 8")
-        if cfg.hidden_act not in _ACT:
-            raise ValueError(f"Dinov2Model: unsupported hidden_act {cfg.hidden_act!r}")
+        check_widths("Dinov2Model", cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size, cfg.hidden_act)
         if cfg.num_channels != 3 or cfg.image_size % cfg.patch_size or cfg.crop_size % cfg.patch_size or cfg.crop_size % 4 \
                 or cfg.resize_shortest_edge < cfg.crop_size:
             raise ValueError("Dinov2Model: 3 channels, image and crop sizes multiples of the patch size, the crop a multiple of 4 and no "
@@ -133,18 +127,9 @@ class Dinov2Model:
         self.config = SimpleNamespace(**cfg.to_dict())
         sd = _canon(state_dict)                                 # embeddings.mask_token, if present, is not read
         want = cfg.state_dict_shapes()
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"DINOv2 state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for k, shp in want.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {tuple(shp)}, got {tuple(sd[k].shape)}")
-        f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
-        half = lambda t: t.to(torch.float16).to(device).contiguous()
-        full = lambda t: t.to(torch.float32).to(device).contiguous()
+        check_state_dict(sd, want, "DINOv2")
+        f32 = lambda k: sd[k].detach().to("cpu", torch.float32) if k in want else None   # a q/k/v bias is read only under qkv_bias
         C = cfg.hidden_size
-        zeros = torch.zeros(C)
-        qkv_b = (lambda k: f32(k)) if cfg.qkv_bias else (lambda k: zeros)
         kp = 3 * cfg.patch_size ** 2
         wp = torch.zeros((C, (kp + 7) // 8 * 8))                 # icd_gemm needs K % 8 == 0: pad columns are zero here and in the patch matrix
         wp[:, :kp] = f32("embeddings.patch_embeddings.projection.weight").reshape(C, kp)
@@ -152,22 +137,15 @@ class Dinov2Model:
         tok = torch.empty((cfg.num_tokens, C))
         tok[0] = f32("embeddings.cls_token")[0, 0] + pos[0, 0]
         tok[1:] = position_table(pos, cfg.crop_size // cfg.patch_size) + f32("embeddings.patch_embeddings.projection.bias")
-        w = {"patch.w": half(wp), "tok": full(tok)}
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layer.{i}."
+        w = {"patch.w": half(wp, device), "tok": full(tok, device)}
+        self.blocks = [f"encoder.layer.{i}." for i in range(cfg.num_hidden_layers)]
+        for p in self.blocks:
             a = p + "attention.attention."
-            w[p + "qk.w"] = half(torch.cat([f32(a + "query.weight"), f32(a + "key.weight")]))
-            w[p + "qk.b"] = full(torch.cat([qkv_b(a + "query.bias"), qkv_b(a + "key.bias")]))
-            w[p + "v.w"] = half(f32(a + "value.weight"))
-            wo, bo = fold_layer_scale(f32(p + "attention.output.dense.weight"), f32(p + "attention.output.dense.bias"),
-                                      f32(p + "layer_scale1.lambda1"), qkv_b(a + "value.bias"))
-            w[p + "o.w"], w[p + "o.b"] = half(wo), full(bo)
-            for n in ("norm1", "norm2"):
-                w[p + n + ".w"], w[p + n + ".b"] = full(f32(p + n + ".weight")), full(f32(p + n + ".bias"))
-            w[p + "fc1.w"], w[p + "fc1.b"] = half(f32(p + "mlp.fc1.weight")), full(f32(p + "mlp.fc1.bias"))
-            w2, b2 = fold_layer_scale(f32(p + "mlp.fc2.weight"), f32(p + "mlp.fc2.bias"), f32(p + "layer_scale2.lambda1"))
-            w[p + "fc2.w"], w[p + "fc2.b"] = half(w2), full(b2)
-        w["ln_f.w"], w["ln_f.b"] = full(f32("layernorm.weight")), full(f32("layernorm.bias"))
+            names = {"q": a + "query", "k": a + "key", "v": a + "value", "out": p + "attention.output.dense", "norm1": p + "norm1",
+                     "norm2": p + "norm2", "fc1": p + "mlp.fc1", "fc2": p + "mlp.fc2"}
+            w.update((p + k, t) for k, t in prepare_block(f32, names, device, lam1=f32(p + "layer_scale1.lambda1"),
+                                                          lam2=f32(p + "layer_scale2.lambda1")).items())
+        w["ln_f.w"], w["ln_f.b"] = full(f32("layernorm.weight"), device), full(f32("layernorm.bias"), device)
         self.w = w
 
     def eval(self):
@@ -192,25 +170,10 @@ class Dinov2Model:
         if patches.dim() != 2 or patches.shape[0] % n or patches.shape[1] != w["patch.w"].shape[1]:
             raise ValueError(f"Dinov2Model: patch matrix must be [B * {n}, {w['patch.w'].shape[1]}], got {tuple(patches.shape)}")
         B = patches.shape[0] // n
-        d, ld = C // H, (T + 7) // 8 * 8
         # no LayerNorm precedes the blocks: the embeddings start the residual stream, so its fp32 twin starts here too
         x, x32 = ops.vit_tokens(ops.gemm(patches, w["patch.w"], out_f32=True), w["tok"], B)
         hs = [x]
-
-        def add(f, wk, bk, x32):
-            n32 = torch.empty(x32.shape, device=x32.device, dtype=torch.float32)
-            return ops.gemm(f, w[wk], w[bk], resid=x32, out32=n32), n32
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layer.{i}."
-            h = ops.layernorm(x, w[p + "norm1.w"], w[p + "norm1.b"], cfg.layer_norm_eps)
-            qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"])
-            vt = ops.project_vt(h, w[p + "v.w"], B, T, ld)
-            o = ops.attention_fused(qk[:, :C], qk[:, C:], vt, B, H, T, T, d, d ** -0.5, causal=False)
-            x, x32 = add(o, p + "o.w", p + "o.b", x32)
-            h = ops.layernorm(x, w[p + "norm2.w"], w[p + "norm2.b"], cfg.layer_norm_eps)
-            f = ops.activation(ops.gemm(h, w[p + "fc1.w"], w[p + "fc1.b"]), _ACT[cfg.hidden_act])
-            x, x32 = add(f, p + "fc2.w", p + "fc2.b", x32)
-            hs.append(x)
+        x, _ = run_blocks(w, self.blocks, x, x32, B, T, H, cfg.layer_norm_eps, cfg.hidden_act, False, hs)
         tok0 = x.reshape(B, T, C)[:, 0].contiguous()           # only the class token is pooled
         pooled = ops.layernorm(tok0, w["ln_f.w"], w["ln_f.b"], cfg.layer_norm_eps).float()
         if output_hidden_states:
@@ -220,8 +183,8 @@ class Dinov2Model:
     def __call__(self, images, output_hidden_states=False):
         out = self.forward_patches(self.preprocess(images), output_hidden_states)
         if output_hidden_states:
-            return TextEncoderOutput(out[0], pooler_output=out[0], hidden_states=out[1])
-        return TextEncoderOutput(out, pooler_output=out)
+            return ModelOutput(out[0], pooler_output=out[0], hidden_states=out[1])
+        return ModelOutput(out, pooler_output=out)
 
     def get_image_features(self, images):
         """what metrics._image_features calls on either encoder: fp32 [B, C] on the device."""

@@ -15,6 +15,7 @@ Weight sources
         W' = W + (alpha / r) * (B @ A)          (convs flattened to matrices; alpha = 8 -> 0.125 at r = 64)
 """
 import dataclasses
+import json
 import os
 import re
 
@@ -112,34 +113,50 @@ def _build_text_encoders(comp, device, dtype, xl):
         comp["text_encoder_2"] = CLIPTextModel(OPENCLIP_BIGG, comp["text_encoder_2_state_dict"], True, device, dtype)
 
 
+def _read_weights(who, *paths, hint=""):
+    """The first of `paths` that exists: a .safetensors file as such, anything else through torch.load(weights_only=True)."""
+    for path in paths:
+        if os.path.exists(path):
+            if path.endswith(".safetensors"):
+                from safetensors.torch import load_file
+                return load_file(path)
+            return torch.load(path, map_location="cpu", weights_only=True)
+    missing = f"{paths[0]} not" if len(paths) == 1 else "neither " + " nor ".join(paths)
+    raise FileNotFoundError(f"{who}: {missing} found{hint}")
+
+
+def _read_json(path):
+    """The object in the JSON file `path`, {} without such a file."""
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return json.load(f)
+
+
+def _override(cfg, fields):
+    """The dataclass `cfg` with those entries of `fields` that it knows."""
+    names = {f.name for f in dataclasses.fields(cfg)}
+    return dataclasses.replace(cfg, **{k: v for k, v in fields.items() if k in names})
+
+
+_LAYOUT = " (want a transformers-layout directory)"
+
+
 def load_clip(path_or_state_dict, device="cuda", dtype=torch.float16, text_config=None, vision_config=None):
     """The joint CLIP model of the edit-quality metrics (metrics.py) on the HIP kernels: a `transformers`-layout directory
     (`config.json` + `model.safetensors`, e.g. a local copy of openai/clip-vit-large-patch14) or a state dict in that layout
     (`text_model.*`, `vision_model.*`, `text_projection.weight`, `visual_projection.weight`).  Configurations default to ViT-L/14; a
     directory's config.json overrides the fields it names."""
-    from .clip import CLIPModel, CLIPTextConfig, CLIPVisionConfig, CLIP_VIT_L, CLIP_VIT_L_VISION
+    from .clip import CLIPModel, CLIP_VIT_L, CLIP_VIT_L_VISION
     tcfg, vcfg = text_config or CLIP_VIT_L, vision_config or CLIP_VIT_L_VISION
     sd = path_or_state_dict
     if isinstance(sd, (str, os.PathLike)):
-        import json
-        from safetensors.torch import load_file
         root = os.fspath(sd)
-        weights = os.path.join(root, "model.safetensors")
-        if not os.path.exists(weights):
-            raise FileNotFoundError(f"load_clip: {weights} not found (want a transformers-layout directory)")
-        cfg_path = os.path.join(root, "config.json")
-        if os.path.exists(cfg_path):
-            with open(cfg_path) as f:
-                cfg = json.load(f)
-
-            def merged(base, section, cls):
-                d = dict(cfg.get(section) or {})
-                if "projection_dim" in cfg:
-                    d.setdefault("projection_dim", cfg["projection_dim"])
-                names = {f.name for f in dataclasses.fields(cls)}
-                return dataclasses.replace(base, **{k: v for k, v in d.items() if k in names})
-            tcfg, vcfg = merged(tcfg, "text_config", CLIPTextConfig), merged(vcfg, "vision_config", CLIPVisionConfig)
-        sd = load_file(weights)
+        sd = _read_weights("load_clip", os.path.join(root, "model.safetensors"), hint=_LAYOUT)
+        cfg = _read_json(os.path.join(root, "config.json"))
+        top = {"projection_dim": cfg["projection_dim"]} if "projection_dim" in cfg else {}     # a section's own value wins
+        tcfg = _override(tcfg, {**top, **(cfg.get("text_config") or {})})
+        vcfg = _override(vcfg, {**top, **(cfg.get("vision_config") or {})})
     return CLIPModel(tcfg, vcfg, sd, device, dtype)
 
 
@@ -148,35 +165,19 @@ def load_dinov2(path_or_state_dict, device="cuda", dtype=torch.float16, config=N
     directory (`config.json` + `model.safetensors` or `pytorch_model.bin`, optionally `preprocessor_config.json`, e.g. a local copy of
     facebook/dinov2-base) or a state dict in that layout.  The configuration defaults to dinov2-base; a directory's config.json overrides
     the fields it names, its preprocessor_config.json the resize and crop sizes."""
-    from .dinov2 import Dinov2Config, Dinov2Model, DINOV2_BASE
+    from .dinov2 import Dinov2Model, DINOV2_BASE
     cfg = config or DINOV2_BASE
     sd = path_or_state_dict
     if isinstance(sd, (str, os.PathLike)):
-        import json
         root = os.fspath(sd)
-        st, pt = os.path.join(root, "model.safetensors"), os.path.join(root, "pytorch_model.bin")
-        if not os.path.exists(st) and not os.path.exists(pt):
-            raise FileNotFoundError(f"load_dinov2: neither {st} nor {pt} found (want a transformers-layout directory)")
-        names = {f.name for f in dataclasses.fields(Dinov2Config)}
-        over = {}
-        cfg_path, pre_path = os.path.join(root, "config.json"), os.path.join(root, "preprocessor_config.json")
-        if os.path.exists(cfg_path):
-            with open(cfg_path) as f:
-                over.update({k: v for k, v in json.load(f).items() if k in names})
-        if os.path.exists(pre_path):
-            with open(pre_path) as f:
-                pre = json.load(f)
-            side = lambda v, key: v.get(key, v.get("height")) if isinstance(v, dict) else v
-            if pre.get("crop_size") is not None:
-                over["crop_size"] = int(side(pre["crop_size"], "height"))
-            if pre.get("size") is not None:
-                over["resize_shortest_edge"] = int(side(pre["size"], "shortest_edge"))
-        cfg = dataclasses.replace(cfg, **over)
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(pt, map_location="cpu", weights_only=True)
+        sd = _read_weights("load_dinov2", os.path.join(root, "model.safetensors"), os.path.join(root, "pytorch_model.bin"), hint=_LAYOUT)
+        cfg = _override(cfg, _read_json(os.path.join(root, "config.json")))
+        pre = _read_json(os.path.join(root, "preprocessor_config.json"))
+        side = lambda v, key: v.get(key, v.get("height")) if isinstance(v, dict) else v
+        if pre.get("crop_size") is not None:
+            cfg = dataclasses.replace(cfg, crop_size=int(side(pre["crop_size"], "height")))
+        if pre.get("size") is not None:
+            cfg = dataclasses.replace(cfg, resize_shortest_edge=int(side(pre["size"], "shortest_edge")))
     return Dinov2Model(cfg, sd, device, dtype)
 
 
@@ -185,17 +186,7 @@ def load_lpips(vgg_path_or_state_dict, lin_path_or_list, device="cuda", config=N
     (`features.<i>.weight / .bias`; `classifier.*` is ignored), or a `.pt` / `.pth` / `.safetensors` file of one.  `lin_path_or_list`: piq's
     `lpips_weights.pt` (a list of five [1, C, 1, 1] tensors), or such a list.  Nothing is downloaded."""
     from .lpips import Lpips, LPIPS_VGG16
-
-    def read(src):
-        if not isinstance(src, (str, os.PathLike)):
-            return src
-        path = os.fspath(src)
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"load_lpips: {path} not found")
-        if path.endswith(".safetensors"):
-            from safetensors.torch import load_file
-            return load_file(path)
-        return torch.load(path, map_location="cpu", weights_only=True)
+    read = lambda src: _read_weights("load_lpips", os.fspath(src)) if isinstance(src, (str, os.PathLike)) else src
     sd = read(vgg_path_or_state_dict)
     sd = {k: v for k, v in sd.items() if k.startswith("features.")}
     lin = read(lin_path_or_list)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .clip import images_to_device
+from .encoder import check_state_dict, image_size, images_to_device, run_by_size
 from .resample import IMAGENET_MEAN, IMAGENET_STD
 
 
@@ -57,13 +57,9 @@ class LpipsConfig:
 LPIPS_VGG16 = LpipsConfig()
 
 
-def _shape(im):
-    return tuple(im.shape[:2]) if hasattr(im, "shape") else im.size[::-1]
-
-
 def _mixed(images):
     """a list that holds images of several sizes"""
-    return isinstance(images, (list, tuple)) and len({_shape(im) for im in images}) > 1
+    return isinstance(images, (list, tuple)) and len({image_size(im) for im in images}) > 1
 
 
 class Lpips:
@@ -75,14 +71,8 @@ class Lpips:
         if cfg.size <= 0 or cfg.size % 4 or cfg.size >> (len(cfg.widths) - 1) < 1:
             raise ValueError(f"Lpips: size must be a multiple of 4 that survives {len(cfg.widths) - 1} poolings, got {cfg.size}")
         self.cfg, self.device = cfg, torch.device(device)
-        want = cfg.state_dict_shapes()
         sd = vgg_state_dict
-        missing = [k for k in want if k not in sd]
-        if missing:
-            raise KeyError(f"VGG16 state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for k, shp in want.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {tuple(shp)}, got {tuple(sd[k].shape)}")
+        check_state_dict(sd, cfg.state_dict_shapes(), "VGG16")
         if len(lin_weights) != len(cfg.widths):
             raise ValueError(f"Lpips: {len(cfg.widths)} lin weights expected, got {len(lin_weights)}")
         f32 = lambda t: t.detach().to("cpu", torch.float32)
@@ -160,12 +150,7 @@ class Lpips:
         a, b = list(images_1), list(images_2)
         if len(a) != len(b):
             raise ValueError(f"Lpips: {len(a)} images against {len(b)}")
-        groups = {}
-        for i, (x, y) in enumerate(zip(a, b)):
-            groups.setdefault((_shape(x), _shape(y)), []).append(i)
-        out = torch.empty((len(a),), device=self.device, dtype=torch.float32)
-        for idx in groups.values():
-            out[torch.as_tensor(idx, device=self.device)] = self._pairs([a[i] for i in idx], [b[i] for i in idx])
-        return out
+        return run_by_size(len(a), lambda i: (image_size(a[i]), image_size(b[i])),
+                           lambda idx: self._pairs([a[i] for i in idx], [b[i] for i in idx]))
 
     __call__ = forward

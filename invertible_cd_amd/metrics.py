@@ -40,21 +40,12 @@ def _count(images):
 
 def _image_features(model, images):
     """fp32 [N, D] on the device.  A list of images of several sizes (the reference's processor takes one) is embedded size by size."""
+    from .encoder import image_size, run_by_size
     if isinstance(images, np.ndarray) and images.ndim == 4:
         images = torch.from_numpy(images)
-    if isinstance(images, (list, tuple)):
-        shape = lambda im: tuple(im.shape[:2]) if isinstance(im, (np.ndarray, torch.Tensor)) else im.size[::-1]
-        groups = {}
-        for i, im in enumerate(images):
-            groups.setdefault(shape(im), []).append(i)
-        if len(groups) > 1:
-            out = None
-            for idx in groups.values():
-                e = model.get_image_features([images[i] for i in idx])
-                out = e.new_empty((len(images), e.shape[1])) if out is None else out
-                out[torch.as_tensor(idx, device=e.device)] = e
-            return out
-    return model.get_image_features(images)
+    if not isinstance(images, (list, tuple)):
+        return model.get_image_features(images)
+    return run_by_size(len(images), lambda i: image_size(images[i]), lambda idx: model.get_image_features([images[i] for i in idx]))
 
 
 def _token_ids(prompts, tokenizer):
@@ -70,33 +61,27 @@ def _token_ids(prompts, tokenizer):
 
 
 @torch.no_grad()
+def _paired_cosine(model, images_1, images_2, batch_size):
+    """Cosine of the embeddings `model` gives corresponding images -> CPU float tensor [N]."""
+    from . import ops
+    n = _count(images_2)
+    assert _count(images_1) == n
+    scores = torch.zeros(n)
+    for i in range(0, n, batch_size):
+        e1 = _image_features(model, images_1[i:i + batch_size])
+        e2 = _image_features(model, images_2[i:i + batch_size])
+        scores[i:i + batch_size] = ops.cosine_rows(e2, e1).cpu()
+    return scores
+
+
 def calc_dinov2_images_images(images_1, images_2, device, batch_size=50, model=None):
     """Cosine of the DINOv2 class-token embeddings of corresponding images -> CPU float tensor [N] (the reference's preservation_dinov2)."""
-    from . import ops
-    model = _need_model(model, "a dinov2.Dinov2Model, e.g. loading.load_dinov2(path)")
-    n = _count(images_2)
-    assert _count(images_1) == n
-    scores = torch.zeros(n)
-    for i in range(0, n, batch_size):
-        e1 = _image_features(model, images_1[i:i + batch_size])
-        e2 = _image_features(model, images_2[i:i + batch_size])
-        scores[i:i + batch_size] = ops.cosine_rows(e2, e1).cpu()
-    return scores
+    return _paired_cosine(_need_model(model, "a dinov2.Dinov2Model, e.g. loading.load_dinov2(path)"), images_1, images_2, batch_size)
 
 
-@torch.no_grad()
 def calc_clip_score_images_images(images_1, images_2, device, batch_size=50, model=None):
     """Cosine of the CLIP image embeddings of corresponding images -> CPU float tensor [N] (the reference's preservation score)."""
-    from . import ops
-    model = _need_model(model)
-    n = _count(images_2)
-    assert _count(images_1) == n
-    scores = torch.zeros(n)
-    for i in range(0, n, batch_size):
-        e1 = _image_features(model, images_1[i:i + batch_size])
-        e2 = _image_features(model, images_2[i:i + batch_size])
-        scores[i:i + batch_size] = ops.cosine_rows(e2, e1).cpu()
-    return scores
+    return _paired_cosine(_need_model(model), images_1, images_2, batch_size)
 
 
 @torch.no_grad()
