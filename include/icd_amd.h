@@ -586,6 +586,43 @@ int icd_lpips_layer(const void* f, int32_t ldf, int32_t B, int32_t HW, int32_t C
 int64_t icd_lpips_layer_workspace_bytes(int32_t B, int32_t HW, int32_t C);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * FID (csrc/inception.hip): the reference's generation metric (utils/metrics.py calculate_fid on utils/inception.py's FID
+ * Inception-v3).  No atomics anywhere: every result is bit-reproducible and does not depend on a sample's position in the batch.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Implicit-GEMM convolution over NHWC fp16: x [B * H * W, ldx] (columns past Cin are not read), w [N, kh * kw * Cin] packed tap-major,
+ * channel-minor, bias fp32 [N] or NULL.  Output pixel (b, yo, xo) reads input pixel (yo * stride - ph + ky, xo * stride - pw + kx);
+ * taps outside the image read zero (and never another sample's rows); Ho = (H + 2 ph - kh) / stride + 1, Wo likewise.  MFMA with fp32
+ * accumulation, then + bias, max(0, .) when relu = 1, rounded to fp16 and stored at out[row * ldo + col_off + n]: a column slice of a
+ * wider matrix (the concat of an Inception block); no other column is written.  Cin % 8 == 0, N % 8 == 0, ldx / ldo / col_off % 8 == 0,
+ * stride 1 or 2, 0 <= ph < kh, 0 <= pw < kw, any M = B * Ho * Wo and any K; pointers 16-byte aligned. */
+int icd_conv2d(const void* x, int32_t ldx, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* w, const float* bias, int32_t N,
+               int32_t kh, int32_t kw, int32_t stride, int32_t ph, int32_t pw, int32_t relu, void* out, int32_t ldo, int32_t col_off,
+               void* stream);
+#define ICD_POOL_MAX_S2    0   /* max, stride 2, no padding, floor: Ho = (H - 3) / 2 + 1                     */
+#define ICD_POOL_MAX_S1P1  1   /* max, stride 1, padding 1: a tap outside the image never wins              */
+#define ICD_POOL_AVG_S1P1  2   /* average, stride 1, padding 1, over the taps inside the image (fp32 sum)   */
+/* 3 x 3 pooling on NHWC fp16 x [B * H * W, ldx] -> out[row * ldo + col_off + c], c < C.  C, ldx, ldo, col_off % 8 == 0, out != x. */
+int icd_pool3x3(const void* x, int32_t ldx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mode, void* out, int32_t ldo,
+                int32_t col_off, void* stream);
+/* out fp32 [B, C] = mean over the HW pixels of x fp16 [B, HW, C], summed in pixel order in double, rounded once.  C % 8 == 0. */
+int icd_global_avgpool(const void* x, int32_t B, int32_t HW, int32_t C, float* out, void* stream);
+/* What pytorch-fid's loader and network do in front of the first convolution, on uint8 NHWC images [B, H, W, 3] (device; `images` may
+ * start at any byte): Resize(S, LANCZOS) (shorter edge to S: resized_h x resized_w, Pillow's antialiased two-pass resample bit for bit,
+ * tables from resample.resample_tables(..., filter='lanczos'), h_* for W -> resized_w, v_* for H -> resized_h), CenterCrop(S) into
+ * mid uint8 [B, S, S, 3] starting at row `top`, column `left` of the resized image (the bytes ToTensor sees), then F.interpolate(mid / 255, (R, R), bilinear, align_corners=False) in fp32 and
+ * out[(b * R + y) * R + x] = 8 fp16 channels: fp16(2 v - 1) for c < 3, zero for 3 .. 7.  With all tables NULL the images are S x S
+ * already and only the last step runs (tmp / mid unused).  tmp: uint8 [B * H * S * 3] scratch, 4-byte aligned; out 16-byte aligned.
+ * Limits: S % 4 == 0 when resizing, W <= 4096.  Three launches. */
+int icd_fid_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t resized_h, int32_t resized_w, int32_t top, int32_t left,
+                   int32_t S, int32_t R, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
+                   const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps, void* tmp, void* mid, void* out,
+                   void* stream);
+/* Streaming FID statistics: sum[d] += sum_i x[i][d], outer[a][b] += sum_i x[i][a] x[i][b] over the rows of x fp32 [n, D], in float64.
+ * The thread that owns an output element starts from the stored value and adds the rows in index order: two calls give the bits of
+ * one call on the concatenation, and sums of several calls (or ranks) simply add.  D % 4 == 0; x 16-byte aligned.  Two launches. */
+int icd_moments_f64(const float* x, int32_t n, int32_t D, double* sum, double* outer, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-kernel-family timing of the executor's launches with HIP events recorded on the launch stream (bench.py's
  * roofline leg).  No reference counterpart (the reference has no timing code at all).
  * ---------------------------------------------------------------------------------------------------------- */

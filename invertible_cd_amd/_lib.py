@@ -35,6 +35,7 @@ ICD_ATTN_Q_PRESCALED = 2
 ICD_ATTN_TUNE_MODE0 = 4
 ICD_HOOK_QUERY = 0
 ICD_HOOK_PROBS = 1
+ICD_POOL_MAX_S2, ICD_POOL_MAX_S1P1, ICD_POOL_AVG_S1P1 = 0, 1, 2
 
 
 class GemmDesc(C.Structure):
@@ -188,6 +189,13 @@ SIGNATURES = {
     "icd_lpips_layer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_int64, C.c_void_p, C.c_void_p]),
     "icd_lpips_layer_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "icd_conv2d": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_int32,
+                                                                                                            C.c_void_p]),
+    "icd_pool3x3": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "icd_global_avgpool": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icd_fid_ingest": (C.c_int, [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
+                       + [C.c_void_p] * 4),
+    "icd_moments_f64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icd_profile_enable": (C.c_int, [C.c_int32]),
     "icd_profile_read": (C.c_int, [C.POINTER(ProfileRow), C.c_int32]),
     "icd_profile_dump": (C.c_int, [C.POINTER(ProfileRecord), C.c_int32]),

@@ -195,6 +195,18 @@ def load_lpips(vgg_path_or_state_dict, lin_path_or_list, device="cuda", config=N
     return Lpips(config or LPIPS_VGG16, sd, list(lin), device)
 
 
+def load_inception(path_or_state_dict, device="cuda", config=None):
+    """The FID network of metrics.calculate_fid on the HIP kernels: pytorch-fid's `pt_inception-2015-12-05-6726825d.pth` (or a `.pt` /
+    `.safetensors` file of the same state dict: `<name>.conv.weight`, `<name>.bn.{weight,bias,running_mean,running_var}`), or such a state
+    dict.  `num_batches_tracked` and the `fc.*` head are ignored.  Nothing is downloaded."""
+    from .inception import FidInception, FID_INCEPTION
+    sd = path_or_state_dict
+    if isinstance(sd, (str, os.PathLike)):
+        sd = _read_weights("load_inception", os.fspath(sd))
+    sd = {k: v for k, v in sd.items() if not k.startswith("fc.") and not k.endswith("num_batches_tracked")}
+    return FidInception(config or FID_INCEPTION, sd, device)
+
+
 def load_models(model_id, device, reverse_checkpoint, forward_checkpoint, r=64, w_embed_dim=0, teacher_checkpoint=None,
                 dtype='fp32', components=None, unet_config=None):
     """SD1.5: (ldm_stable, reverse_cons_model, forward_cons_model).  `components` may supply real

@@ -7,6 +7,8 @@ reference's utils/metrics.py).
     calculate_psnr(images_1, images_2, device, batch_size=50)                                utils/metrics.py:295-308
     calculate_lpips(images_1, images_2, device, batch_size=50, model=...)
     calc_inversion(path_to_dir, device, dinov2_model=..., lpips_model=...)
+    get_activations / calculate_activation_statistics / calculate_frechet_distance / compute_statistics_of_path /
+    save_statistics_of_path / calculate_fid(images, path, device=None, batch_size=40, dims=2048, ..., model=...)    utils/metrics.py:40-171
 
 Names, argument order and return values are the reference's; `model=` is what the reference fetched from the hub on every call
 (`AutoModel.from_pretrained('openai/clip-vit-large-patch14')`: a clip.CLIPModel, e.g. from loading.load_clip;
@@ -16,7 +18,10 @@ e.g. from loading.load_lpips).  Images may be PIL images, numpy uint8 HWC arrays
 and scored (icd_cosine_rows / icd_lpips_layer) without a copy to the host.  A list may mix image sizes (each size
 is preprocessed as one batch); a tensor or array holds one size.  `prompts` are token ids [N, T]
 (as everywhere in this package) or strings together with `tokenizer=`.  LPIPS is computed from its definition (a VGG16 feature stack,
-lpips.py) rather than through `piq`; ImageReward and FID stay out: their packages (and weights) are not available.
+lpips.py) rather than through `piq`, and FID from its own (the FID Inception-v3 of inception.py, `model=` an inception.FidInception, e.g.
+from loading.load_inception; the statistics stream through FidStatistics / icd_moments_f64 on the device, the Frechet distance itself is
+float64 scipy on the host, as in the reference; dims other than 2048 are refused).  ImageReward stays out: its package and weights are
+not available.
 """
 import json
 import math
@@ -183,3 +188,167 @@ def calc_inversion(path_to_dir, device, dinov2_model=None, lpips_model=None):
     with open(os.path.join(path_to_dir, "preservation_metrics_values.json"), "w") as fp:
         json.dump(report, fp)
     return report
+
+
+# ------------------------------------------------------------------------------------------------------------ FID
+IMAGE_EXTENSIONS = {'bmp', 'jpg', 'jpeg', 'pgm', 'png', 'ppm', 'tif', 'tiff', 'webp'}
+INCEPTION_PATH = "files/pt_inception-2015-12-05-6726825d.pth"
+
+
+def _check_dims(dims):
+    if dims != 2048:
+        raise ValueError(f"metrics: FID is computed on the pooled features (dims=2048) only, got dims={dims}")
+
+
+def _fid_model(model, inception_path, device):
+    if model is not None:
+        return model
+    from .loading import load_inception
+    return load_inception(inception_path, device="cuda" if device is None else device)
+
+
+def _open_images(images):
+    """file names in a list become PIL images; everything else passes"""
+    if isinstance(images, (list, tuple)) and len(images) and isinstance(images[0], (str, os.PathLike)):
+        from PIL import Image
+        return [Image.open(p).convert("RGB") for p in images]
+    return images
+
+
+def _feature_batches(images, model, batch_size):
+    for i in range(0, _count(images), batch_size):
+        yield i, model.features(_open_images(images[i:i + batch_size]))
+
+
+class FidStatistics:
+    """Streaming mean and covariance of feature rows: n, sum x and sum x x^T in float64.  `update` adds a batch of fp32 features on the
+    device (icd_moments_f64: fixed order, no atomics); sums of several accumulators - batches, ranks - simply add (`merge`, `add`)."""
+
+    def __init__(self):
+        self.n, self.total, self.outer = 0, None, None
+
+    def add(self, n, total, outer):
+        """add raw sums: n rows, sum x [D], sum x x^T [D, D] (numpy or torch, any device)"""
+        as64 = lambda t: (t.detach().to(torch.float64) if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t, np.float64))).clone()
+        total, outer = as64(total), as64(outer)
+        if self.total is None:
+            self.total, self.outer = total, outer
+        else:
+            if total.shape != self.total.shape:
+                raise ValueError(f"FidStatistics: features of width {total.shape[0]} added to sums of width {self.total.shape[0]}")
+            self.total += total.to(self.total.device)
+            self.outer += outer.to(self.outer.device)
+        self.n += int(n)
+        return self
+
+    def update(self, features):
+        """features: fp32 [n, D] on the device"""
+        from . import ops
+        if features.dim() != 2 or not features.is_cuda:
+            raise ValueError("FidStatistics.update: features must be a device tensor [n, D]")
+        f = features.to(torch.float32).contiguous()
+        if self.total is None:
+            D = f.shape[1]
+            self.total = torch.zeros((D,), device=f.device, dtype=torch.float64)
+            self.outer = torch.zeros((D, D), device=f.device, dtype=torch.float64)
+        ops.moments_f64(f, self.total, self.outer)
+        self.n += f.shape[0]
+        return self
+
+    def merge(self, other):
+        return self.add(other.n, other.total, other.outer) if other.n else self
+
+    def finalize(self):
+        """(mu [D], sigma [D, D]) as float64 numpy arrays: np.mean(x, axis=0) and np.cov(x, rowvar=False) (n - 1 in the denominator)."""
+        if self.n < 2:
+            raise ValueError(f"FidStatistics: {self.n} rows are too few for a covariance")
+        total, outer = self.total.cpu().numpy(), self.outer.cpu().numpy()
+        mu = total / self.n
+        return mu, (outer - self.n * np.outer(mu, mu)) / (self.n - 1)
+
+
+@torch.no_grad()
+def get_activations(images, model, batch_size=50, dims=2048, device='cpu', num_workers=8):
+    """The pooled Inception features of every image -> float64 numpy [N, model.cfg.dims] (the reference's pred_arr).  `images`: PIL
+    images, numpy uint8 HWC arrays, file names, or a uint8 NHWC tensor on the device; the loader's Resize(256, LANCZOS) + CenterCrop(256)
+    runs on the device (icd_fid_ingest).  `device` and `num_workers` are the reference's arguments; the model's device is used."""
+    _check_dims(dims)
+    n = _count(images)
+    if batch_size > n:
+        print(f'get_activations: batch_size {batch_size} exceeds the {n} images; using {n}')
+        batch_size = n
+    pred_arr = np.empty((n, model.cfg.dims))
+    for i, f in _feature_batches(images, model, batch_size):
+        pred_arr[i:i + f.shape[0]] = f.cpu().numpy()
+    return pred_arr
+
+
+@torch.no_grad()
+def calculate_activation_statistics(images, model, batch_size=50, dims=2048, device='cpu', num_workers=8):
+    """(mu, sigma) of the pooled features: np.mean(act, axis=0), np.cov(act, rowvar=False), accumulated batch by batch on the device
+    (FidStatistics) - the [N, 2048] activations never exist on the host."""
+    _check_dims(dims)
+    stats = FidStatistics()
+    for _, f in _feature_batches(images, model, max(1, min(batch_size, _count(images)))):
+        stats.update(f)
+    return stats.finalize()
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """d^2 = |mu1 - mu2|^2 + tr(sigma1) + tr(sigma2) - 2 tr sqrt(sigma1 sigma2), in float64 on the host (scipy.linalg.sqrtm): the
+    reference's arithmetic, off the hot path.  When the root of the product comes back with non-finite entries (a singular product),
+    it is taken again with eps added to both diagonals, and a line says so; a root whose diagonal has an imaginary part beyond 1e-3 is
+    an error, a smaller imaginary part is numerical noise and is dropped."""
+    from scipy import linalg
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    sigma1, sigma2 = np.atleast_2d(np.asarray(sigma1, np.float64)), np.atleast_2d(np.asarray(sigma2, np.float64))
+    if mu1.shape != mu2.shape:
+        raise ValueError(f"calculate_frechet_distance: mean vectors of lengths {mu1.shape} and {mu2.shape}")
+    if sigma1.shape != sigma2.shape:
+        raise ValueError(f"calculate_frechet_distance: covariances of shapes {sigma1.shape} and {sigma2.shape}")
+
+    def root(a, b):
+        r = linalg.sqrtm(a @ b)
+        return r[0] if isinstance(r, tuple) else r
+    half = root(sigma1, sigma2)
+    if not np.all(np.isfinite(half)):
+        print(f"calculate_frechet_distance: sqrt(sigma1 sigma2) is not finite (singular product); retrying with {eps} on both diagonals")
+        ridge = eps * np.identity(sigma1.shape[0])
+        half = root(sigma1 + ridge, sigma2 + ridge)
+    if np.iscomplexobj(half):
+        worst = float(np.abs(np.diagonal(half).imag).max())
+        if worst > 1e-3:
+            raise ValueError(f"calculate_frechet_distance: sqrt(sigma1 sigma2) has an imaginary diagonal of up to {worst}")
+        half = half.real
+    delta = mu1 - mu2
+    return float(delta @ delta) + float(np.trace(sigma1)) + float(np.trace(sigma2)) - 2.0 * float(np.trace(half))
+
+
+def compute_statistics_of_path(path, model, batch_size, dims, device, num_workers=8):
+    """(mu, sigma) from an `.npz` with `mu` / `sigma`, or of the image files of a directory (sorted by name)."""
+    path = os.fspath(path)
+    if path.endswith('.npz'):
+        with np.load(path) as f:
+            return f['mu'][:], f['sigma'][:]
+    files = sorted(os.path.join(path, name) for name in os.listdir(path) if name.rsplit('.', 1)[-1].lower() in IMAGE_EXTENSIONS)
+    return calculate_activation_statistics(files, model, batch_size, dims, device, num_workers)
+
+
+def save_statistics_of_path(path, out_path, device=None, batch_size=50, dims=2048, num_workers=8, inception_path=INCEPTION_PATH, model=None):
+    """The statistics of a directory of images, written as the `.npz` that calculate_fid reads."""
+    _check_dims(dims)
+    model = _fid_model(model, inception_path, device)
+    m1, s1 = compute_statistics_of_path(path, model, batch_size, dims, device, num_workers)
+    np.savez(out_path, mu=m1, sigma=s1)
+
+
+def calculate_fid(images, path, device=None, batch_size=40, dims=2048, num_workers=4, inception_path=INCEPTION_PATH, model=None):
+    """FID of `images` against the statistics of `path` (an `.npz` or a directory of images).  model=: an inception.FidInception, e.g.
+    loading.load_inception(path); without it `inception_path` is read from disk.  Nothing is downloaded."""
+    _check_dims(dims)
+    if not os.path.exists(path):
+        raise RuntimeError(f'calculate_fid: {path} does not exist (want an .npz of statistics or a directory of images)')
+    model = _fid_model(model, inception_path, device)
+    m1, s1 = calculate_activation_statistics(images, model, batch_size, dims, device, num_workers)
+    m2, s2 = compute_statistics_of_path(path, model, batch_size, dims, device, num_workers)
+    return calculate_frechet_distance(m1, s1, m2, s2)

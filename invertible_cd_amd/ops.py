@@ -715,3 +715,111 @@ def lpips_layer(f, B, HW, w, out=None, relu=False, accumulate=False):
     _lib.check(lib.icd_lpips_layer(_p(f), f.stride(0), B, HW, Cc, _p(w), int(relu), int(accumulate), _p(ws), n, _p(out), _stream()),
                "icd_lpips_layer")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ FID (Inception-v3)
+def pack_conv_weight_hw(w_oihw, pad_cin_to=8):
+    """[O, I, kh, kw] (any kh, kw) -> [O, kh*kw*I'] fp16, tap-major, channel-minor like pack_conv_weight; I is padded with zero channels to
+    a multiple of `pad_cin_to` (the 3-channel image arrives as 8 channels)."""
+    o, i, kh, kw = w_oihw.shape
+    ip = (i + pad_cin_to - 1) // pad_cin_to * pad_cin_to
+    if ip != i:
+        w = w_oihw.new_zeros((o, ip, kh, kw))
+        w[:, :i] = w_oihw
+        w_oihw = w
+    return w_oihw.permute(0, 2, 3, 1).reshape(o, -1).to(torch.float16).contiguous()
+
+
+def _slice_out(out, rows, n, col_off, device):
+    """The output matrix of a kernel that writes a column slice: a fresh [rows, n] one, or the caller's wider `out`."""
+    if out is None:
+        assert col_off == 0
+        return torch.empty((rows, n), device=device, dtype=torch.float16)
+    assert out.is_cuda and out.dtype == torch.float16 and out.dim() == 2 and out.is_contiguous() and out.shape[0] == rows \
+        and col_off + n <= out.shape[1], f"out {tuple(out.shape)} does not hold [{rows}, {col_off} : {col_off + n}]"
+    return out
+
+
+def conv2d_out_size(H, W, kh, kw, stride, ph, pw):
+    return (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
+
+
+def conv2d(x, B, H, W, w_packed, bias, kh, kw, stride=1, ph=0, pw=0, relu=True, out=None, col_off=0):
+    """icd_conv2d: NHWC fp16 x [B * H * W, Cin] (a row-major matrix or a column slice of one) * w_packed [N, kh * kw * Cin] (+ fp32 bias,
+    ReLU) -> columns col_off .. col_off + N of `out` [B * Ho * Wo, ldo] (a fresh [B * Ho * Wo, N] without out=)."""
+    _chk_rows(x, "x"); _chk16(w_packed, "w")
+    Cin, N = x.shape[1], w_packed.shape[0]
+    assert x.shape[0] == B * H * W, f"conv2d: x {tuple(x.shape)} is not [{B} * {H} * {W}, Cin]"
+    assert w_packed.shape[1] == kh * kw * Cin, f"conv2d: w {tuple(w_packed.shape)} is not [N, {kh} * {kw} * {Cin}]"
+    assert bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+    Ho, Wo = conv2d_out_size(H, W, kh, kw, stride, ph, pw)
+    out = _slice_out(out, B * Ho * Wo, N, col_off, x.device)
+    _lib.check(_lib.load().icd_conv2d(_p(x), x.stride(0), B, H, W, Cin, _p(w_packed), _p(bias), N, kh, kw, stride, ph, pw, int(relu), _p(out),
+                                      out.stride(0), col_off, _stream()), "icd_conv2d")
+    return out
+
+
+def pool3x3(x, B, H, W, mode, out=None, col_off=0):
+    """icd_pool3x3 over NHWC fp16 x [B * H * W, C]; mode _lib.ICD_POOL_MAX_S2 / ICD_POOL_MAX_S1P1 / ICD_POOL_AVG_S1P1 -> columns
+    col_off .. col_off + C of `out` (a fresh [B * Ho * Wo, C] without out=)."""
+    _chk_rows(x, "x")
+    Cc = x.shape[1]
+    assert x.shape[0] == B * H * W, f"pool3x3: x {tuple(x.shape)} is not [{B} * {H} * {W}, C]"
+    Ho, Wo = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == _lib.ICD_POOL_MAX_S2 else (H, W)
+    out = _slice_out(out, B * Ho * Wo, Cc, col_off, x.device)
+    _lib.check(_lib.load().icd_pool3x3(_p(x), x.stride(0), B, H, W, Cc, mode, _p(out), out.stride(0), col_off, _stream()), "icd_pool3x3")
+    return out
+
+
+def global_avgpool(x, B, HW):
+    """fp16 [B * HW, C] -> fp32 [B, C]: the spatial mean (icd_global_avgpool)."""
+    _chk16(x, "x")
+    Cc = x.shape[-1]
+    assert x.numel() == B * HW * Cc, f"global_avgpool: x {tuple(x.shape)} is not [{B} * {HW}, C]"
+    out = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().icd_global_avgpool(_p(x), B, HW, Cc, _p(out), _stream()), "icd_global_avgpool")
+    return out
+
+
+_LANCZOS_DEV = {}
+
+
+def fid_ingest(images, crop=256, size=299):
+    """uint8 NHWC images [B, H, W, 3] on the device -> (fp16 [B * size * size, 8], uint8 [B, crop, crop, 3]): torchvision's
+    Resize(crop, LANCZOS) + CenterCrop(crop) (the returned uint8 intermediate: the bytes ToTensor sees), then the network's own bilinear
+    resize to size x size and 2 x - 1 (icd_fid_ingest).  crop = 0: the images are taken as they are (square), only the bilinear step runs."""
+    from . import resample
+    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
+        "fid_ingest: need a contiguous cuda uint8 [B, H, W, 3] tensor"
+    B, H, W, _ = images.shape
+    out = torch.empty((B * size * size, 8), device=images.device, dtype=torch.float16)
+    if not crop:
+        assert H == W, f"fid_ingest: crop = 0 takes square images, got {H} x {W}"
+        _lib.check(_lib.load().icd_fid_ingest(_p(images), B, H, W, H, W, 0, 0, H, size, *([None, None, None, 0] * 2), None, None, _p(out),
+                                              _stream()), "icd_fid_ingest")
+        return out, images
+    rh, rw, top, left = resample.fid_geometry(H, W, crop)
+
+    def tables(n_in, n_out):
+        key = (n_in, n_out, str(images.device))
+        if key not in _LANCZOS_DEV:
+            _LANCZOS_DEV[key] = tuple(torch.from_numpy(t.copy()).to(images.device).contiguous()
+                                      for t in resample.resample_tables(n_in, n_out, "lanczos"))
+        return _LANCZOS_DEV[key]
+    hf, hc, hk = tables(W, rw)
+    vf, vc, vk = tables(H, rh)
+    tmp = torch.empty((B * H, crop, 3), device=images.device, dtype=torch.uint8)
+    mid = torch.empty((B, crop, crop, 3), device=images.device, dtype=torch.uint8)
+    _lib.check(_lib.load().icd_fid_ingest(_p(images), B, H, W, rh, rw, top, left, crop, size, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf),
+                                          _p(vc), _p(vk), vk.shape[1], _p(tmp), _p(mid), _p(out), _stream()), "icd_fid_ingest")
+    return out, mid
+
+
+def moments_f64(x, total, outer):
+    """total [D] += sum of the rows of x fp32 [n, D], outer [D, D] += sum of their outer products, in float64 on the device
+    (icd_moments_f64: fixed order, two calls equal one call on the concatenation bit for bit)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous(), "moments_f64: x must be contiguous cuda fp32 [n, D]"
+    n, D = x.shape
+    assert total.is_cuda and total.dtype == torch.float64 and total.is_contiguous() and tuple(total.shape) == (D,)
+    assert outer.is_cuda and outer.dtype == torch.float64 and outer.is_contiguous() and tuple(outer.shape) == (D, D)
+    _lib.check(_lib.load().icd_moments_f64(_p(x), n, D, _p(total), _p(outer), _stream()), "icd_moments_f64")

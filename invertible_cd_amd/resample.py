@@ -28,22 +28,40 @@ def _bicubic(x, a=-0.5):
     return 0.0
 
 
-def tap_width(in_size, out_size):
-    """Row length of the coefficient table (Pillow's ksize): 2 * ceil(support) + 1 with support = 2 * max(in / out, 1)."""
-    return int(math.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+def _lanczos(x):
+    """Pillow's lanczos_filter (support 3): sinc(x) sinc(x / 3)"""
+    def sinc(v):
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v
+    return sinc(x) * sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
+
+
+FILTERS = {"bicubic": (_bicubic, 2.0), "lanczos": (_lanczos, 3.0)}      # name -> (kernel, support)
+
+
+def tap_width(in_size, out_size, filter="bicubic"):
+    """Row length of the coefficient table (Pillow's ksize): 2 * ceil(support) + 1 with support = 2 (bicubic) or 3 (lanczos) times
+    max(in / out, 1)."""
+    return int(math.ceil(FILTERS[filter][1] * max(in_size / out_size, 1.0))) * 2 + 1
 
 
 @functools.lru_cache(maxsize=64)
-def resample_tables(in_size, out_size):
+def resample_tables(in_size, out_size, filter="bicubic"):
     """One axis of the resample: (first [out] int32, count [out] int32, coef [out, tap_width] int32, zero padded).
+    filter: 'bicubic' (Pillow's BICUBIC, the default) or 'lanczos' (Pillow's LANCZOS, what the FID loader resizes with).
 
     Output pixel i is clip8((sum_k coef[i, k] * in[first[i] + k] + 2^21) >> 22) over k < count[i]."""
     if in_size <= 0 or out_size <= 0:
         raise ValueError(f"resample_tables: sizes must be positive, got {in_size} -> {out_size}")
+    if filter not in FILTERS:
+        raise ValueError(f"resample_tables: unknown filter {filter!r} (want one of {sorted(FILTERS)})")
+    kernel, width = FILTERS[filter]
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
-    support = 2.0 * filterscale
-    ksize = tap_width(in_size, out_size)
+    support = width * filterscale
+    ksize = tap_width(in_size, out_size, filter)
     first = np.zeros(out_size, np.int32)
     count = np.zeros(out_size, np.int32)
     coef = np.zeros((out_size, ksize), np.int32)
@@ -52,7 +70,7 @@ def resample_tables(in_size, out_size):
         center = (i + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = np.array([_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)], np.float64)
+        w = np.array([kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)], np.float64)
         total = 0.0
         for v in w:                               # Pillow sums in tap order; keep the order so the double result is the same
             total += v
@@ -89,13 +107,25 @@ def _pass(img, tables, axis):
     return np.moveaxis(out, 0, axis)
 
 
-def resize_emulated(img, out_h, out_w):
-    """numpy restatement of the two integer passes on a uint8 [H, W, C] image (what the device kernel computes)."""
+def resize_emulated(img, out_h, out_w, filter="bicubic", skip_identity=True):
+    """numpy restatement of the two integer passes on a uint8 [H, W, C] image (what the device kernel computes).  Pillow skips a pass
+    whose size does not change; the device kernels run it (skip_identity=False) - its table is the identity."""
     img = np.asarray(img)
     assert img.dtype == np.uint8 and img.ndim == 3
     h, w = img.shape[:2]
-    if out_w != w:                                # Pillow skips a pass whose size does not change
-        img = _pass(img, resample_tables(w, out_w), 1)
-    if out_h != h:
-        img = _pass(img, resample_tables(h, out_h), 0)
+    if out_w != w or not skip_identity:
+        img = _pass(img, resample_tables(w, out_w, filter), 1)
+    if out_h != h or not skip_identity:
+        img = _pass(img, resample_tables(h, out_h, filter), 0)
     return img
+
+
+def fid_geometry(height, width, size=256):
+    """(resized_h, resized_w, top, left) of torchvision's Resize(size) + CenterCrop(size): the shorter edge goes to `size`, the longer one
+    to int(size * long / short), the crop starts at int(round((resized - size) / 2.0))."""
+    if height <= 0 or width <= 0:
+        raise ValueError(f"fid_geometry: bad image size {height} x {width}")
+    short, long = (width, height) if width <= height else (height, width)
+    new_long = int(size * long / short)
+    rh, rw = (new_long, size) if width <= height else (size, new_long)
+    return rh, rw, int(round((rh - size) / 2.0)), int(round((rw - size) / 2.0))

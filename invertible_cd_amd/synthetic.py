@@ -268,3 +268,31 @@ def synthetic_lpips_state(cfg, seed: int = 0, device="cpu", dtype=torch.float32)
         sd[key] = t.to(dtype)
     lin = [torch.rand((1, w, 1, 1), generator=_gen(f"lpips:lin{i}", seed, device), device=device).to(dtype) for i, w in enumerate(cfg.widths)]
     return sd, lin
+
+
+def synthetic_inception_state(cfg, seed: int = 0, device="cpu", dtype=torch.float32):
+    """A state dict of inception.FidInception in pytorch-fid's `pt_inception-2015-12-05` layout (`<name>.conv.weight`, `<name>.bn.*`
+    with `num_batches_tracked`, and the `fc.*` head that the loader ignores): He-scaled convolutions N(0, 2 / (kh kw Cin)), BatchNorm
+    weight 1 + 0.1 N, bias 0.05 N, running_mean 0.1 N, running_var U(0.8, 1.2) - a BasicConv2d then keeps the second moment of its input,
+    and the activations stay O(1) through the stem and all eleven blocks (largest stored activation on the tests' structured images: 6.9, 11.5
+    and 8.6 for seeds 0, 1, 2 at full width - tests/test_fid.py recomputes them -, 6.1 for the reduced network; fp16 reaches 65504)."""
+    sd = {}
+    for key, shape in cfg.state_dict_shapes().items():
+        g = _gen("inception:" + key, seed, device)
+        if key.endswith(".conv.weight"):
+            t = torch.randn(shape, generator=g, device=device) * (2.0 / (shape[1] * shape[2] * shape[3])) ** 0.5
+        elif key.endswith(".bn.weight"):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g, device=device)
+        elif key.endswith(".bn.bias"):
+            t = 0.05 * torch.randn(shape, generator=g, device=device)
+        elif key.endswith(".running_mean"):
+            t = 0.1 * torch.randn(shape, generator=g, device=device)
+        else:
+            t = 0.8 + 0.4 * torch.rand(shape, generator=g, device=device)
+        sd[key] = t.to(dtype)
+        if key.endswith(".running_var"):
+            sd[key[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(0, device=device)
+    g = _gen("inception:fc", seed, device)
+    sd["fc.weight"] = (torch.randn((1008, cfg.dims), generator=g, device=device) * cfg.dims ** -0.5).to(dtype)
+    sd["fc.bias"] = torch.zeros((1008,), device=device, dtype=dtype)
+    return sd
