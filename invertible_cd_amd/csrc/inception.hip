@@ -3,11 +3,9 @@
 //                       v_mfma_f32_16x16x32_f16; fp32 bias and ReLU in the epilogue; writes a column slice of a wider row (the concat)
 //   icd_pool3x3         the three 3 x 3 poolings of the network, into a column slice as well
 //   icd_global_avgpool  fp16 [B, HW, C] -> fp32 [B, C]
-//   icd_fid_ingest      uint8 images -> Pillow LANCZOS shorter-edge resize + centre crop (uint8) -> bilinear -> 2 u / 255 - 1, fp16 x 8
 //   icd_moments_f64     streaming sum x and sum x x^T in float64
 // 64-bit row offsets everywhere; no atomics: every sum has a fixed order and no result depends on a sample's position in the batch.
 #include "common.h"
-#include "resample_pass.h"
 
 namespace {
 
@@ -189,61 +187,6 @@ __global__ __launch_bounds__(256) void global_avgpool_kernel(const half_t* x, lo
     for (int j = 0; j < 8; ++j) out[b * C + c8 + j] = (float)(acc[j] / (double)HW);
 }
 
-// ------------------------------------------------------------------------------------------------------------------------- ingest
-// Vertical pass of the LANCZOS resize, cropped: one thread owns one pixel of the uint8 [B, S, S, 3] intermediate - the bytes ToTensor
-// would see.
-__global__ __launch_bounds__(256) void fid_resample_v_kernel(PreK p, unsigned char* mid) {
-    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long SS = (long long)p.S * p.S;
-    if (it >= p.B * SS) return;
-    const long long b = it / SS;
-    const int rem = (int)(it - b * SS), y = rem / p.S, x = rem - y * p.S;
-    const int rowb = p.S * 3;
-    const int f = max(p.vfirst[y], 0);
-    const int n = min(p.vcount[y], min(p.vk, p.H - f));         // clamped: a wrong table cannot read outside the image
-    const int* kk = p.vcoef + (long long)y * p.vk;
-    const unsigned char* col = p.tmp + (b * p.H + f) * (long long)rowb + x * 3;
-    int acc[3] = {0, 0, 0};
-    for (int k = 0; k < n; ++k) {
-        const int w = kk[k];
-        const unsigned char* s = col + (long long)k * rowb;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += w * (int)s[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mid[it * 3 + c] = (unsigned char)clip8(acc[c]);
-}
-
-// F.interpolate(u / 255, (R, R), mode='bilinear', align_corners=False), then 2 v - 1: one thread owns one output pixel, one 16-byte
-// store (channels 3 .. 7 zero: the Cin = 8 layout of the first convolution).  The roundings are spelled out (no contraction but the
-// fmaf written here): source index fma(scale, i + 0.5, -0.5), rows fma(1 - lx, p0, lx p1), columns likewise - what torch's CPU kernel
-// evaluates, so the fp32 value is the same; near 2 v - 1 = 0 one fp32 ulp of v is worth several fp16 ulps of the result.
-__global__ __launch_bounds__(256) void fid_bilinear_kernel(const unsigned char* mid, long long B, int S, int R, half_t* out) {
-#pragma clang fp contract(off)
-    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long RR = (long long)R * R;
-    if (it >= B * RR) return;
-    const long long b = it / RR;
-    const int rem = (int)(it - b * RR), y = rem / R, x = rem - y * R;
-    const float scale = (float)S / (float)R;
-    const float sy = fmaxf(fmaf(scale, (float)y + 0.5f, -0.5f), 0.f), sx = fmaxf(fmaf(scale, (float)x + 0.5f, -0.5f), 0.f);
-    const int y0 = min((int)sy, S - 1), x0 = min((int)sx, S - 1);
-    const int y1 = min(y0 + 1, S - 1), x1 = min(x0 + 1, S - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const unsigned char* img = mid + b * S * S * 3;
-    const unsigned char *p00 = img + ((long long)y0 * S + x0) * 3, *p01 = img + ((long long)y0 * S + x1) * 3;
-    const unsigned char *p10 = img + ((long long)y1 * S + x0) * 3, *p11 = img + ((long long)y1 * S + x1) * 3;
-    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float a = (float)p00[c] / 255.0f, bq = (float)p01[c] / 255.0f, cq = (float)p10[c] / 255.0f, d = (float)p11[c] / 255.0f;
-        const float top = fmaf(1.f - lx, a, lx * bq), bot = fmaf(1.f - lx, cq, lx * d);
-        const float u = fmaf(1.f - ly, top, ly * bot);
-        v[c] = (half_t)(2.0f * u - 1.0f);
-    }
-    *reinterpret_cast<f16x8*>(out + it * 8) = v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------ moments
 // outer[a][b] += sum_i x[i][a] x[i][b] in double.  A thread owns a 4 x 4 patch of `outer`, starts from the value that is there and adds
 // the rows in index order (the product of two floats is exact in double): two calls give the bits of one call on the concatenation.
@@ -276,11 +219,6 @@ __global__ __launch_bounds__(256) void moments_sum_kernel(const float* x, int n,
     double acc = sum[d];
     for (int i = 0; i < n; ++i) acc += (double)x[(long long)i * D + d];
     sum[d] = acc;
-}
-
-inline int lanczos_taps(int in, int o) {
-    const double s = (double)in / o;
-    return (int)ceil(3.0 * (s > 1.0 ? s : 1.0)) * 2 + 1;
 }
 
 }  // namespace
@@ -347,53 +285,6 @@ extern "C" int icd_global_avgpool(const void* x, int32_t B, int32_t HW, int32_t 
     ICD_CHECK_ARG(blocks <= 0x7fffffffLL, "icd_global_avgpool: %lld blocks exceed the grid limit", blocks);
     hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, total, HW, vpr, out);
     ICD_CHECK_LAUNCH("icd_global_avgpool");
-    return ICD_OK;
-}
-
-extern "C" int icd_fid_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t resized_h, int32_t resized_w, int32_t top, int32_t left,
-                              int32_t S, int32_t R, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps, const int32_t* v_first,
-                              const int32_t* v_count, const int32_t* v_coef, int32_t v_taps, void* tmp, void* mid, void* out, void* stream) {
-    ICD_CHECK_ARG(images && out, "icd_fid_ingest: null pointer");
-    ICD_CHECK_ARG(B > 0, "icd_fid_ingest: B must be positive (got %d)", B);
-    ICD_CHECK_ARG(H > 0 && W > 0 && S > 0 && R > 0 && S <= 4096 && R <= 4096, "icd_fid_ingest: sizes must be positive, S and R at most 4096");
-    ICD_CHECK_ARG(((uintptr_t)out & 15) == 0, "icd_fid_ingest: out must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const long long opix = (long long)B * R * R;
-    ICD_CHECK_ARG((opix + 255) / 256 <= 0x7fffffffLL, "icd_fid_ingest: the batch exceeds the grid limit");
-    const unsigned char* src = (const unsigned char*)images;
-    if (h_first || v_first) {
-        ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_fid_ingest: null coefficient table");
-        ICD_CHECK_ARG(tmp && mid, "icd_fid_ingest: the resize needs tmp and mid");
-        ICD_CHECK_ARG(S % 4 == 0, "icd_fid_ingest: S must be a multiple of 4 (got %d)", S);
-        ICD_CHECK_ARG(W <= 4096, "icd_fid_ingest: image width %d exceeds 4096", W);
-        ICD_CHECK_ARG(top >= 0 && left >= 0 && top + S <= resized_h && left + S <= resized_w,
-                      "icd_fid_ingest: the crop of %d at (%d, %d) does not lie inside the resized image (%d x %d)", S, top, left, resized_h,
-                      resized_w);
-        ICD_CHECK_ARG(((uintptr_t)tmp & 3) == 0, "icd_fid_ingest: tmp must be 4-byte aligned");
-        ICD_CHECK_ARG(h_taps == lanczos_taps(W, resized_w) && v_taps == lanczos_taps(H, resized_h),
-                      "icd_fid_ingest: tables do not match the sizes (taps %d / %d, expected %d / %d)", h_taps, v_taps, lanczos_taps(W, resized_w),
-                      lanczos_taps(H, resized_h));
-        const long long pixels = (long long)B * S * S;
-        ICD_CHECK_ARG((pixels + 255) / 256 <= 0x7fffffffLL && ((long long)B * H + HROWS - 1) / HROWS <= 0x7fffffffLL,
-                      "icd_fid_ingest: the batch exceeds the grid limit");
-        PreK p;
-        p.img = src; p.tmp = (unsigned char*)tmp; p.out = (half_t*)out;
-        p.hfirst = h_first + left; p.hcount = h_count + left; p.hcoef = h_coef + (long long)left * h_taps;
-        p.vfirst = v_first + top; p.vcount = v_count + top; p.vcoef = v_coef + (long long)top * v_taps;
-        p.B = B; p.H = H; p.W = W; p.S = S; p.P = 1; p.G = S; p.ldo = 8; p.hk = h_taps; p.vk = v_taps;
-        p.rows = (long long)B * H;
-        for (int c = 0; c < 3; ++c) { p.mean[c] = 0.f; p.stdv[c] = 1.f; }
-        const size_t lds_h = (size_t)HROWS * W * 3 + 32;
-        hipLaunchKernelGGL(clip_resample_h_kernel, dim3((unsigned)((p.rows + HROWS - 1) / HROWS)), dim3(256), lds_h, st, p);
-        ICD_CHECK_LAUNCH("icd_fid_ingest (horizontal)");
-        hipLaunchKernelGGL(fid_resample_v_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, p, (unsigned char*)mid);
-        ICD_CHECK_LAUNCH("icd_fid_ingest (vertical)");
-        src = (const unsigned char*)mid;
-    } else {
-        ICD_CHECK_ARG(H == S && W == S, "icd_fid_ingest: without tables the images must be S x S already (got %d x %d, S %d)", H, W, S);
-    }
-    hipLaunchKernelGGL(fid_bilinear_kernel, dim3((unsigned)((opix + 255) / 256)), dim3(256), 0, st, src, (long long)B, S, R, (half_t*)out);
-    ICD_CHECK_LAUNCH("icd_fid_ingest (bilinear)");
     return ICD_OK;
 }
 

@@ -1,41 +1,10 @@
-// LPIPS on the device (invertible_cd_amd/lpips.py): the ingest of uint8 images (Pillow's BICUBIC stretch to S x S, ImageNet normalisation,
-// NHWC fp16 padded to 8 channels), the ReLU and 2 x 2 max-pool between the 3 x 3 convolutions of the VGG16 stack (which are icd_gemm's),
-// and the distance head: channel normalisation, squared difference, per-channel weights, spatial mean.  All are bandwidth kernels with
-// 16-byte accesses and 64-bit row offsets; no float atomics, every sum has a fixed order.
+// LPIPS on the device (invertible_cd_amd/lpips.py): the ReLU and 2 x 2 max-pool between the 3 x 3 convolutions of the VGG16 stack (which
+// are icd_gemm's), and the distance head: channel normalisation, squared difference, per-channel weights, spatial mean.  All are
+// bandwidth kernels with 16-byte accesses and 64-bit row offsets; no float atomics, every sum has a fixed order.  (The ingest of the
+// uint8 images, icd_image_resize_norm, is ingest.hip's.)
 #include "common.h"
-#include "resample_pass.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------------------------------ ingest
-// Vertical pass + normalise.  One thread owns one output pixel: three byte columns of the horizontal pass's rows, one 16-byte store
-// (channels 0 .. 2 the normalised pixel, 3 .. 7 zero: the Cin = 8 layout of the first convolution).
-__global__ __launch_bounds__(256) void resize_norm_v_kernel(PreK p) {
-    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long SS = (long long)p.S * p.S;
-    if (it >= p.B * SS) return;
-    const long long b = it / SS;
-    const int rem = (int)(it - b * SS), y = rem / p.S, x = rem - y * p.S;
-    const int rowb = p.S * 3;
-    const int f = max(p.vfirst[y], 0);
-    const int n = min(p.vcount[y], min(p.vk, p.H - f));         // clamped: a wrong table cannot read outside the image
-    const int* kk = p.vcoef + (long long)y * p.vk;
-    const unsigned char* col = p.tmp + (b * p.H + f) * (long long)rowb + x * 3;
-    int acc[3] = {0, 0, 0};
-    for (int k = 0; k < n; ++k) {
-        const int w = kk[k];
-        const unsigned char* s = col + (long long)k * rowb;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += w * (int)s[c];
-    }
-    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float u = (float)clip8(acc[c]);
-        v[c] = (half_t)((u / 255.0f - p.mean[c]) / p.stdv[c]);
-    }
-    *reinterpret_cast<f16x8*>(p.out + it * 8) = v;
-}
 
 // ------------------------------------------------------------------------------------------------------------------ ReLU, max-pool
 __device__ __forceinline__ f16x8 relu8(f16x8 v) {
@@ -180,40 +149,6 @@ __global__ __launch_bounds__(64) void lpips_finish_kernel(const float* partial, 
 }
 
 }  // namespace
-
-extern "C" int icd_image_resize_norm(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first,
-                                     const int32_t* h_count, const int32_t* h_coef, int32_t h_taps, const int32_t* v_first,
-                                     const int32_t* v_count, const int32_t* v_coef, int32_t v_taps, const float* mean, const float* stdv,
-                                     void* tmp, void* out, void* stream) {
-    ICD_CHECK_ARG(images && tmp && out && mean && stdv, "icd_image_resize_norm: null pointer");
-    ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_image_resize_norm: null coefficient table");
-    ICD_CHECK_ARG(B > 0, "icd_image_resize_norm: B must be positive (got %d)", B);
-    ICD_CHECK_ARG(H > 0 && W > 0, "icd_image_resize_norm: image sizes must be positive (got %d x %d)", H, W);
-    ICD_CHECK_ARG(S > 0 && S % 4 == 0 && S <= 4096, "icd_image_resize_norm: S must be a positive multiple of 4, <= 4096 (got %d)", S);
-    ICD_CHECK_ARG(W <= 4096, "icd_image_resize_norm: image width %d exceeds 4096", W);
-    ICD_CHECK_ARG(((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out & 15) == 0,
-                  "icd_image_resize_norm: tmp must be 4-byte aligned, out 16-byte aligned");
-    auto taps = [](int in, int o) { const double s = (double)in / o; return (int)ceil(2.0 * (s > 1.0 ? s : 1.0)) * 2 + 1; };
-    ICD_CHECK_ARG(h_taps == taps(W, S) && v_taps == taps(H, S),
-                  "icd_image_resize_norm: tables do not match the sizes (taps %d / %d, expected %d / %d)", h_taps, v_taps, taps(W, S), taps(H, S));
-    for (int c = 0; c < 3; ++c) ICD_CHECK_ARG(stdv[c] > 0.f, "icd_image_resize_norm: std must be positive");
-    const long long pixels = (long long)B * S * S;
-    ICD_CHECK_ARG((pixels + 255) / 256 <= 0x7fffffffLL && ((long long)B * H + HROWS - 1) / HROWS <= 0x7fffffffLL,
-                  "icd_image_resize_norm: the batch exceeds the grid limit");
-    PreK p;
-    p.img = (const unsigned char*)images; p.tmp = (unsigned char*)tmp; p.out = (half_t*)out;
-    p.hfirst = h_first; p.hcount = h_count; p.hcoef = h_coef; p.vfirst = v_first; p.vcount = v_count; p.vcoef = v_coef;
-    p.B = B; p.H = H; p.W = W; p.S = S; p.P = 1; p.G = S; p.ldo = 8; p.hk = h_taps; p.vk = v_taps;
-    p.rows = (long long)B * H;
-    for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds_h = (size_t)HROWS * W * 3 + 32;
-    hipLaunchKernelGGL(clip_resample_h_kernel, dim3((unsigned)((p.rows + HROWS - 1) / HROWS)), dim3(256), lds_h, st, p);
-    ICD_CHECK_LAUNCH("icd_image_resize_norm (horizontal)");
-    hipLaunchKernelGGL(resize_norm_v_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, p);
-    ICD_CHECK_LAUNCH("icd_image_resize_norm (vertical)");
-    return ICD_OK;
-}
 
 extern "C" int icd_relu(const void* x, int64_t n, void* out, void* stream) {
     ICD_CHECK_ARG(x && out, "icd_relu: null pointer");

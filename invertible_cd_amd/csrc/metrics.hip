@@ -1,54 +1,8 @@
-// Edit-quality metrics on the device: CLIP / DINOv2 image preprocessing (Pillow's BICUBIC resample, bit for bit), the token assembly of
-// a ViT's embeddings, row-wise cosine, and the exact integer sum of squared differences behind PSNR.  All are bandwidth kernels; the
-// resample arithmetic is restated from Pillow's documented behaviour (invertible_cd_amd/resample.py builds the coefficient tables).
+// Edit-quality metrics on the device: the token assembly of a ViT's embeddings, row-wise cosine, and the exact integer sum of squared
+// differences behind PSNR.  All are bandwidth kernels.  (The image preprocessing of CLIP / DINOv2 is ingest.hip's.)
 #include "common.h"
-#include "resample_pass.h"
 
 namespace {
-
-// Vertical pass + crop + normalise + patch scatter.  One block owns one row of patches (P output rows): the resampled bytes go to LDS,
-// then the G patch-matrix rows leave as 16-byte stores in column order (c * P + py) * P + px, pad columns zero.
-__global__ __launch_bounds__(256) void clip_resample_v_kernel(PreK p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // [P, S * 3]
-    const int b = blockIdx.x / p.G, pr = blockIdx.x - b * p.G;
-    const int rowb = p.S * 3, wpr = rowb / 4;
-    const unsigned char* src = p.tmp + (long long)b * p.H * rowb;
-    for (int it = threadIdx.x; it < p.P * wpr; it += blockDim.x) {
-        const int yy = it / wpr, wd = it - yy * wpr;
-        const int y = pr * p.P + yy;
-        const int f = max(p.vfirst[y], 0);
-        const int n = min(p.vcount[y], min(p.vk, p.H - f));
-        const int* kk = p.vcoef + (long long)y * p.vk;
-        const unsigned char* col = src + (long long)f * rowb + wd * 4;
-        unsigned packed = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                          // four neighbouring bytes of each tap row: one 4-byte segment per lane
-            int acc = 0;
-            for (int k = 0; k < n; ++k) acc += kk[k] * (int)col[(long long)k * rowb + j];
-            packed |= clip8(acc) << (8 * j);
-        }
-        *reinterpret_cast<unsigned*>(lds + yy * rowb + wd * 4) = packed;
-    }
-    __syncthreads();
-    const int PP = p.P * p.P, cols = 3 * PP, vpr = p.ldo / 8;
-    half_t* out = p.out + ((long long)b * p.G + pr) * p.G * p.ldo;
-    for (int it = threadIdx.x; it < p.G * vpr; it += blockDim.x) {
-        const int px_blk = it / vpr, c8 = (it - px_blk * vpr) * 8;
-        f16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int col = c8 + j;
-            float f = 0.f;
-            if (col < cols) {
-                const int c = col / PP, rem = col - c * PP, py = rem / p.P, px = rem - py * p.P;
-                const float u = (float)lds[py * rowb + (px_blk * p.P + px) * 3 + c];
-                f = (u / 255.0f - p.mean[c]) / p.stdv[c];
-            }
-            v[j] = (half_t)f;
-        }
-        *reinterpret_cast<f16x8*>(out + (long long)px_blk * p.ldo + c8) = v;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------- ViT token assembly
 // One thread owns 8 consecutive columns of one output row: two 16-byte loads from the token table (and from the patch GEMM's fp32
@@ -150,47 +104,6 @@ __global__ __launch_bounds__(256) void sq_diff_sum_u8_kernel(const unsigned char
 }
 
 }  // namespace
-
-extern "C" int icd_clip_preprocess(const void* images, int32_t B, int32_t H, int32_t W, int32_t resized_h, int32_t resized_w, int32_t crop,
-                                   int32_t patch, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
-                                   const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps,
-                                   const float* mean, const float* stdv, void* tmp, void* out, int32_t ldo, void* stream) {
-    ICD_CHECK_ARG(images && tmp && out && mean && stdv, "icd_clip_preprocess: null pointer");
-    ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_clip_preprocess: null coefficient table");
-    ICD_CHECK_ARG(B > 0, "icd_clip_preprocess: B must be positive (got %d)", B);
-    ICD_CHECK_ARG(H > 0 && W > 0 && resized_h > 0 && resized_w > 0, "icd_clip_preprocess: sizes must be positive");
-    ICD_CHECK_ARG(patch > 0 && crop > 0 && crop % patch == 0 && crop % 4 == 0 && crop <= 1024 && patch <= 64,
-                  "icd_clip_preprocess: crop must be a multiple of the patch size and of 4, <= 1024");
-    ICD_CHECK_ARG(resized_h >= crop && resized_w >= crop, "icd_clip_preprocess: the resized image (%d x %d) is smaller than the crop %d",
-                  resized_h, resized_w, crop);
-    ICD_CHECK_ARG(ldo % 8 == 0 && ldo >= 3 * patch * patch, "icd_clip_preprocess: ldo must be a multiple of 8, >= 3 * patch^2");
-    ICD_CHECK_ARG(W <= 4096, "icd_clip_preprocess: image width %d exceeds 4096", W);
-    ICD_CHECK_ARG(((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out & 15) == 0,
-                  "icd_clip_preprocess: tmp must be 4-byte aligned, out 16-byte aligned");
-    ICD_CHECK_ARG((long long)patch * crop * 3 <= 65536, "icd_clip_preprocess: patch * crop * 3 = %lld bytes of LDS exceed 64 KiB",
-                  (long long)patch * crop * 3);
-    // the tables' row length follows from the sizes (Pillow: 2 * ceil(2 * max(in / out, 1)) + 1): a table built for other sizes is refused
-    auto taps = [](int in, int o) { const double s = (double)in / o; return (int)ceil(2.0 * (s > 1.0 ? s : 1.0)) * 2 + 1; };
-    ICD_CHECK_ARG(h_taps == taps(W, resized_w) && v_taps == taps(H, resized_h),
-                  "icd_clip_preprocess: tables do not match the sizes (taps %d / %d, expected %d / %d)", h_taps, v_taps, taps(W, resized_w),
-                  taps(H, resized_h));
-    for (int c = 0; c < 3; ++c) ICD_CHECK_ARG(stdv[c] > 0.f, "icd_clip_preprocess: std must be positive");
-    PreK p;
-    p.img = (const unsigned char*)images; p.tmp = (unsigned char*)tmp; p.out = (half_t*)out;
-    const int left = (resized_w - crop) / 2, top = (resized_h - crop) / 2;
-    p.hfirst = h_first + left; p.hcount = h_count + left; p.hcoef = h_coef + (long long)left * h_taps;
-    p.vfirst = v_first + top; p.vcount = v_count + top; p.vcoef = v_coef + (long long)top * v_taps;
-    p.B = B; p.H = H; p.W = W; p.S = crop; p.P = patch; p.G = crop / patch; p.ldo = ldo; p.hk = h_taps; p.vk = v_taps;
-    p.rows = (long long)B * H;
-    for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds_h = (size_t)HROWS * W * 3 + 32;
-    hipLaunchKernelGGL(clip_resample_h_kernel, dim3((unsigned)((p.rows + HROWS - 1) / HROWS)), dim3(256), lds_h, st, p);
-    ICD_CHECK_LAUNCH("icd_clip_preprocess (horizontal)");
-    hipLaunchKernelGGL(clip_resample_v_kernel, dim3((unsigned)(B * p.G)), dim3(256), (size_t)patch * crop * 3, st, p);
-    ICD_CHECK_LAUNCH("icd_clip_preprocess (vertical)");
-    return ICD_OK;
-}
 
 extern "C" int icd_vit_tokens(const float* acc, int32_t lda, const float* tok, int32_t B, int32_t n, int32_t C, void* out16, float* out32,
                               void* stream) {

@@ -134,9 +134,23 @@ def images_to_device(images, device):
     return t.to(device).contiguous()
 
 
+def image_batch_to_device(images, device):
+    """images_to_device for the models that also take a stacked uint8 NHWC ndarray as a batch (images_to_device itself takes an ndarray
+    for ONE image, and the CLIP and DINOv2 towers, which call it directly, refuse a stacked one)."""
+    import numpy as np
+    if isinstance(images, np.ndarray) and images.ndim == 4:
+        images = torch.from_numpy(np.ascontiguousarray(images))
+    return images_to_device(images, device)
+
+
 def image_size(im):
     """(height, width) of a PIL image or an HWC array or tensor"""
     return tuple(im.shape[:2]) if hasattr(im, "shape") else im.size[::-1]
+
+
+def mixed_sizes(images):
+    """a list that holds images of several sizes"""
+    return isinstance(images, (list, tuple)) and len({image_size(im) for im in images}) > 1
 
 
 def run_by_size(n, key, run):

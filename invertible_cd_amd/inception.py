@@ -18,11 +18,10 @@ branch of a block stores straight into its column slice of the block's output: n
 """
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import _lib, ops
-from .encoder import check_state_dict, image_size, images_to_device, run_by_size
+from .encoder import check_state_dict, image_batch_to_device, image_size, mixed_sizes, run_by_size
 
 BN_EPS = 1e-3
 MAX_S2, MAX_S1P1, AVG = "max_s2", "max_s1p1", "avg"
@@ -158,11 +157,6 @@ def folded_weights(cfg, state_dict):
     return out
 
 
-def _mixed(images):
-    """a list that holds images of several sizes"""
-    return isinstance(images, (list, tuple)) and len({image_size(im) for im in images}) > 1
-
-
 class FidInception:
     def __init__(self, cfg: InceptionConfig, state_dict, device="cuda"):
         if cfg.div < 1 or cfg.crop < 0 or cfg.crop % 4 or cfg.size < 0:
@@ -180,15 +174,10 @@ class FidInception:
         return self
 
     # ------------------------------------------------------------------------------------------------------- front end
-    def _to_device(self, images):
-        if isinstance(images, np.ndarray) and images.ndim == 4:  # a stacked array is a batch, not one image
-            images = torch.from_numpy(np.ascontiguousarray(images))
-        return images_to_device(images, self.device)
-
     def ingest(self, images):
         """PIL images / numpy uint8 HWC arrays / a stacked uint8 NHWC array or tensor (one size) ->
         (fp16 [B * s * s, 8] network input, uint8 [B, crop, crop, 3] the loader's output, B, s)."""
-        t = self._to_device(images)
+        t = image_batch_to_device(images, self.device)
         cfg = self.cfg
         if not cfg.crop and t.shape[1] != t.shape[2]:
             raise ValueError(f"FidInception: crop = 0 takes square images, got {tuple(t.shape[1:3])}")
@@ -268,7 +257,7 @@ class FidInception:
     def features(self, images):
         """fp32 [N, dims] on the device.  A list may mix image sizes: each size is ingested as one batch, the rows come back in the
         caller's order."""
-        if not _mixed(images):
+        if not mixed_sizes(images):
             return self._blocks_one_size(images)[-1]
         items = list(images)
         return run_by_size(len(items), lambda i: image_size(items[i]), lambda idx: self._blocks_one_size([items[i] for i in idx])[-1])

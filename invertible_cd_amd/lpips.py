@@ -17,11 +17,10 @@ convolution runs here.
 """
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import ops
-from .encoder import check_state_dict, image_size, images_to_device, run_by_size
+from .encoder import check_state_dict, image_batch_to_device, image_size, mixed_sizes, run_by_size
 from .resample import IMAGENET_MEAN, IMAGENET_STD
 
 
@@ -55,11 +54,6 @@ class LpipsConfig:
 
 
 LPIPS_VGG16 = LpipsConfig()
-
-
-def _mixed(images):
-    """a list that holds images of several sizes"""
-    return isinstance(images, (list, tuple)) and len({image_size(im) for im in images}) > 1
 
 
 class Lpips:
@@ -104,9 +98,7 @@ class Lpips:
 
     def ingest(self, images):
         """PIL images / numpy uint8 HWC arrays / a stacked uint8 NHWC array or tensor (one size) -> (fp16 [B * size * size, 8], B)."""
-        if isinstance(images, np.ndarray) and images.ndim == 4:  # a stacked array is a batch, not one image (as metrics._image_features)
-            images = torch.from_numpy(np.ascontiguousarray(images))
-        t = images_to_device(images, self.device)
+        t = image_batch_to_device(images, self.device)
         return ops.image_resize_norm(t, self.cfg.size, self.cfg.mean, self.cfg.std), t.shape[0]
 
     def _stack(self, x, B, tap):
@@ -145,7 +137,7 @@ class Lpips:
     def forward(self, images_1, images_2):
         """fp32 [N] on the device.  A list may mix image sizes (each side of a pair is resized on its own): the pairs are ingested size by
         size and the scores come back in the caller's order."""
-        if not _mixed(images_1) and not _mixed(images_2):
+        if not mixed_sizes(images_1) and not mixed_sizes(images_2):
             return self._pairs(images_1, images_2)
         a, b = list(images_1), list(images_2)
         if len(a) != len(b):

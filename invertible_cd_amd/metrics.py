@@ -14,7 +14,7 @@ Names, argument order and return values are the reference's; `model=` is what th
 (`AutoModel.from_pretrained('openai/clip-vit-large-patch14')`: a clip.CLIPModel, e.g. from loading.load_clip;
 `AutoModel.from_pretrained('facebook/dinov2-base')`: a dinov2.Dinov2Model, e.g. from loading.load_dinov2; `piq.LPIPS()`: a lpips.Lpips,
 e.g. from loading.load_lpips).  Images may be PIL images, numpy uint8 HWC arrays, or a uint8 NHWC tensor on the device
-(generation.runner(..., return_type='uint8_device')), which is preprocessed (icd_clip_preprocess / icd_image_resize_norm), embedded
+(generation.runner(..., return_type='uint8_device')), which is preprocessed (icd_clip_preprocess / icd_image_resize_norm, csrc/ingest.hip), embedded
 and scored (icd_cosine_rows / icd_lpips_layer) without a copy to the host.  A list may mix image sizes (each size
 is preprocessed as one batch); a tensor or array holds one size.  `prompts` are token ids [N, T]
 (as everywhere in this package) or strings together with `tokenizer=`.  LPIPS is computed from its definition (a VGG16 feature stack,
@@ -45,10 +45,10 @@ def _count(images):
 
 def _image_features(model, images):
     """fp32 [N, D] on the device.  A list of images of several sizes (the reference's processor takes one) is embedded size by size."""
-    from .encoder import image_size, run_by_size
-    if isinstance(images, np.ndarray) and images.ndim == 4:
-        images = torch.from_numpy(images)
-    if not isinstance(images, (list, tuple)):
+    from .encoder import image_batch_to_device, image_size, mixed_sizes, run_by_size
+    if isinstance(images, np.ndarray):                          # a stacked array is a batch: the towers themselves refuse one
+        images = image_batch_to_device(images, model.device)
+    if not mixed_sizes(images):
         return model.get_image_features(images)
     return run_by_size(len(images), lambda i: image_size(images[i]), lambda idx: model.get_image_features([images[i] for i in idx]))
 

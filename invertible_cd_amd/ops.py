@@ -595,17 +595,31 @@ def accumulate_multi(dst, src):
         _lib.check(lib.icd_accumulate_multi(dp, sp, cn, n, _stream()), "icd_accumulate_multi")
 
 
-# ------------------------------------------------------------------------------------------------ edit-quality metrics
+# ------------------------------------------------------------------------------------------------ image ingest (csrc/ingest.hip)
 _RESAMPLE_DEV = {}
 
 
-def _resample_tables_dev(in_size, out_size, device):
-    """resample.resample_tables on the device (int32), cached per (sizes, device): uploaded once, read by every later call."""
-    key = (in_size, out_size, str(device))
+def _resample_tables_dev(in_size, out_size, device, filter="bicubic"):
+    """resample.resample_tables on the device (int32), cached per (sizes, device, filter): uploaded once, read by every later call."""
+    key = (in_size, out_size, str(device), filter)
     if key not in _RESAMPLE_DEV:
         from . import resample
-        _RESAMPLE_DEV[key] = tuple(torch.from_numpy(t.copy()).to(device).contiguous() for t in resample.resample_tables(in_size, out_size))
+        _RESAMPLE_DEV[key] = tuple(torch.from_numpy(t.copy()).to(device).contiguous()
+                                   for t in resample.resample_tables(in_size, out_size, filter))
     return _RESAMPLE_DEV[key]
+
+
+def _chk_images(images, name):
+    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
+        f"{name}: need a contiguous cuda uint8 [B, H, W, 3] tensor"
+    return images.shape[:3]
+
+
+def _table_args(W, rw, H, rh, device, filter="bicubic"):
+    """The tables of a W -> rw, H -> rh resample as the C functions take them: (first, count, coef, tap width) of the horizontal pass,
+    then of the vertical one.  (The tensors behind the pointers live in the cache.)"""
+    (hf, hc, hk), (vf, vc, vk) = _resample_tables_dev(W, rw, device, filter), _resample_tables_dev(H, rh, device, filter)
+    return _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf), _p(vc), _p(vk), vk.shape[1]
 
 
 def clip_preprocess(images, size=224, crop=224, patch=14, mean=None, std=None):
@@ -613,20 +627,16 @@ def clip_preprocess(images, size=224, crop=224, patch=14, mean=None, std=None):
     transformers.CLIPImageProcessor (Pillow BICUBIC shortest-edge resize, centre crop, normalise), columns as patch_embedding.weight
     flattens (icd_clip_preprocess)."""
     from . import resample
-    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
-        "clip_preprocess: need a contiguous cuda uint8 [B, H, W, 3] tensor"
-    B, H, W, _ = images.shape
+    B, H, W = _chk_images(images, "clip_preprocess")
     rh, rw, _, _ = resample.clip_geometry(H, W, size, crop)
-    hf, hc, hk = _resample_tables_dev(W, rw, images.device)
-    vf, vc, vk = _resample_tables_dev(H, rh, images.device)
     g = crop // patch
     ldo = (3 * patch * patch + 7) // 8 * 8
     tmp = torch.empty((B * H, crop, 3), device=images.device, dtype=torch.uint8)
     out = torch.empty((B * g * g, ldo), device=images.device, dtype=torch.float16)
     m3 = (C.c_float * 3)(*(mean or resample.CLIP_MEAN))
     s3 = (C.c_float * 3)(*(std or resample.CLIP_STD))
-    _lib.check(_lib.load().icd_clip_preprocess(_p(images), B, H, W, rh, rw, crop, patch, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf), _p(vc),
-                                               _p(vk), vk.shape[1], m3, s3, _p(tmp), _p(out), ldo, _stream()), "icd_clip_preprocess")
+    _lib.check(_lib.load().icd_clip_preprocess(_p(images), B, H, W, rh, rw, crop, patch, *_table_args(W, rw, H, rh, images.device), m3, s3,
+                                               _p(tmp), _p(out), ldo, _stream()), "icd_clip_preprocess")
     return out
 
 
@@ -667,16 +677,12 @@ def sq_diff_sum_u8(a, b):
 def image_resize_norm(images, size, mean, std):
     """uint8 NHWC images [B, H, W, 3] on the device -> fp16 [B * size * size, 8]: np.array(PIL.Image.resize((size, size))) / 255 (Pillow's
     BICUBIC, both axes stretched, no crop), normalised, channels 3 .. 7 zero (icd_image_resize_norm)."""
-    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
-        "image_resize_norm: need a contiguous cuda uint8 [B, H, W, 3] tensor"
-    B, H, W, _ = images.shape
-    hf, hc, hk = _resample_tables_dev(W, size, images.device)
-    vf, vc, vk = _resample_tables_dev(H, size, images.device)
+    B, H, W = _chk_images(images, "image_resize_norm")
     tmp = torch.empty((B * H, size, 3), device=images.device, dtype=torch.uint8)
     out = torch.empty((B * size * size, 8), device=images.device, dtype=torch.float16)
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    _lib.check(_lib.load().icd_image_resize_norm(_p(images), B, H, W, size, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf), _p(vc), _p(vk),
-                                                 vk.shape[1], m3, s3, _p(tmp), _p(out), _stream()), "icd_image_resize_norm")
+    _lib.check(_lib.load().icd_image_resize_norm(_p(images), B, H, W, size, *_table_args(W, size, H, size, images.device), m3, s3, _p(tmp),
+                                                 _p(out), _stream()), "icd_image_resize_norm")
     return out
 
 
@@ -781,17 +787,12 @@ def global_avgpool(x, B, HW):
     return out
 
 
-_LANCZOS_DEV = {}
-
-
 def fid_ingest(images, crop=256, size=299):
     """uint8 NHWC images [B, H, W, 3] on the device -> (fp16 [B * size * size, 8], uint8 [B, crop, crop, 3]): torchvision's
     Resize(crop, LANCZOS) + CenterCrop(crop) (the returned uint8 intermediate: the bytes ToTensor sees), then the network's own bilinear
     resize to size x size and 2 x - 1 (icd_fid_ingest).  crop = 0: the images are taken as they are (square), only the bilinear step runs."""
     from . import resample
-    assert images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(), \
-        "fid_ingest: need a contiguous cuda uint8 [B, H, W, 3] tensor"
-    B, H, W, _ = images.shape
+    B, H, W = _chk_images(images, "fid_ingest")
     out = torch.empty((B * size * size, 8), device=images.device, dtype=torch.float16)
     if not crop:
         assert H == W, f"fid_ingest: crop = 0 takes square images, got {H} x {W}"
@@ -799,19 +800,10 @@ def fid_ingest(images, crop=256, size=299):
                                               _stream()), "icd_fid_ingest")
         return out, images
     rh, rw, top, left = resample.fid_geometry(H, W, crop)
-
-    def tables(n_in, n_out):
-        key = (n_in, n_out, str(images.device))
-        if key not in _LANCZOS_DEV:
-            _LANCZOS_DEV[key] = tuple(torch.from_numpy(t.copy()).to(images.device).contiguous()
-                                      for t in resample.resample_tables(n_in, n_out, "lanczos"))
-        return _LANCZOS_DEV[key]
-    hf, hc, hk = tables(W, rw)
-    vf, vc, vk = tables(H, rh)
     tmp = torch.empty((B * H, crop, 3), device=images.device, dtype=torch.uint8)
     mid = torch.empty((B, crop, crop, 3), device=images.device, dtype=torch.uint8)
-    _lib.check(_lib.load().icd_fid_ingest(_p(images), B, H, W, rh, rw, top, left, crop, size, _p(hf), _p(hc), _p(hk), hk.shape[1], _p(vf),
-                                          _p(vc), _p(vk), vk.shape[1], _p(tmp), _p(mid), _p(out), _stream()), "icd_fid_ingest")
+    _lib.check(_lib.load().icd_fid_ingest(_p(images), B, H, W, rh, rw, top, left, crop, size, *_table_args(W, rw, H, rh, images.device, "lanczos"),
+                                          _p(tmp), _p(mid), _p(out), _stream()), "icd_fid_ingest")
     return out, mid
 
 

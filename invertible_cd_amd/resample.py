@@ -3,7 +3,7 @@
 `PIL.Image.resize(size, BICUBIC)` is an antialiased two-pass separable resample (horizontal pass, then vertical): the cubic filter
 (a = -0.5) is stretched by the scale factor when shrinking, each output pixel's taps are normalised in double, rounded to fixed point
 with 22 fractional bits, and both passes accumulate in int32 and clip to uint8.  Once the tables exist the arithmetic is pure integer,
-so `icd_clip_preprocess` (csrc/metrics.hip) reproduces it bit for bit.  This module is numpy only: it builds the tables, states the
+so `icd_clip_preprocess` (csrc/ingest.hip) reproduces it bit for bit.  This module is numpy only: it builds the tables, states the
 shortest-edge / centre-crop geometry of `transformers.CLIPImageProcessor`, and carries a numpy emulation of the two passes (the CPU
 test's check of the tables against Pillow itself; the device kernel is checked against Pillow on the GPU).
 """

@@ -37,6 +37,22 @@ def test_the_default_tables_are_the_bicubic_ones_unchanged():
         resample.resample_tables(8, 8, filter="box")
 
 
+def test_the_device_table_cache_keeps_the_filters_apart():
+    """ops._resample_tables_dev holds BICUBIC and LANCZOS tables in one cache: the filter is part of the key, so neither is handed out
+    for the other, a second call uploads nothing, and the bicubic entry is resample.resample_tables as it stands."""
+    from invertible_cd_amd import ops, resample
+    n_in, n_out = 300, 256
+    bic, lan = ops._resample_tables_dev(n_in, n_out, "cpu", "bicubic"), ops._resample_tables_dev(n_in, n_out, "cpu", "lanczos")
+    assert all(a is b for a, b in zip(bic, ops._resample_tables_dev(n_in, n_out, "cpu", "bicubic")))
+    assert all(a is b for a, b in zip(bic, ops._resample_tables_dev(n_in, n_out, "cpu")))                # bicubic is the default
+    assert all(a is b for a, b in zip(lan, ops._resample_tables_dev(n_in, n_out, "cpu", "lanczos")))
+    assert not torch.equal(bic[2], lan[2])                      # the coefficients: another support, another row length
+    for filt, got in (("bicubic", bic), ("lanczos", lan)):
+        want = resample.resample_tables(n_in, n_out, filt)
+        assert len(got) == len(want) == 3
+        assert all(g.dtype == torch.int32 and torch.equal(g, torch.from_numpy(w.copy())) for g, w in zip(got, want))
+
+
 def _spd(rng, d, n=None):
     x = rng.standard_normal((n or 4 * d, d)) @ rng.standard_normal((d, d))
     return x.mean(0), np.cov(x, rowvar=False)
