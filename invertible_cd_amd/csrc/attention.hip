@@ -1105,16 +1105,10 @@ template <int KS, int DT, int QT, int OCC, int NST, int MODE, bool CAUSAL, int D
 int launch_attn_c(AttnK k, hipStream_t st) {
     constexpr int smem = NST * (64 * 2 * KS * 16 + (DR ? DR * 16 : DT * 32) * 128);
     static_assert(smem * OCC <= 160 * 1024, "LDS ring x occupancy exceeds the CU's 160 KiB");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fused_kernel<KS, DT, QT, OCC, NST, MODE, CAUSAL, DR>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> armed{0};
     k.nqt = (k.Nq + 128 * QT - 1) / (128 * QT);
-    hipLaunchKernelGGL((attn_fused_kernel<KS, DT, QT, OCC, NST, MODE, CAUSAL, DR>), dim3(k.nqt * k.B * k.H), dim3(256), smem, st, k);
-    ICD_CHECK_LAUNCH("icd_attention_fused");
-    return ICD_OK;
+    return icd_launch_lds(armed, "icd_attention_fused", &attn_fused_kernel<KS, DT, QT, OCC, NST, MODE, CAUSAL, DR>, dim3(k.nqt * k.B * k.H), dim3(256),
+                          smem, st, k);
 }
 template <int KS, int DT, int QT, int OCC = 2, int NST = 2, int MODE = 0, int DR = 0>
 int launch_attn(AttnK k, hipStream_t st) {

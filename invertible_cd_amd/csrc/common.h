@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include "../../include/icd_amd.h"
 
 typedef _Float16 half_t;
@@ -33,6 +34,25 @@ void icd_set_error(const char* fmt, ...);
     } while (0)
 
 #ifdef __HIPCC__
+// Launch of a kernel whose dynamic LDS exceeds the 64 KiB a function gets by default.  hipFuncAttributeMaxDynamicSharedMemorySize
+// belongs to the function ON ONE DEVICE: it is set before the first launch on each device.  `armed` is the caller's mask of the devices
+// done, one `static std::atomic<unsigned long long>` per kernel instantiation.  Host threads may race to the first launch: each of
+// them sets the same value before it launches, which is harmless.  Afterwards the launch path makes no HIP call but hipGetDevice.
+template <typename... P, typename... A>
+int icd_launch_lds(std::atomic<unsigned long long>& armed, const char* what, void (*kernel)(P...), dim3 grid, dim3 block, int smem,
+                   hipStream_t st, const A&... args) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = (unsigned)dev < 64u ? 1ull << dev : 0ull;       // (a device past the mask is set on every launch)
+    if (!(armed.load(std::memory_order_acquire) & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess)
+            armed.fetch_or(bit, std::memory_order_release);       // (a failure shows as this launch's error and is tried again on the next)
+    }
+    hipLaunchKernelGGL(kernel, grid, block, smem, st, args...);
+    ICD_CHECK_LAUNCH(what);
+    return ICD_OK;
+}
+
 // 16 bytes of zeros for out-of-bounds im2col taps / ragged tiles (global_load_lds needs a real source address)
 static __device__ __attribute__((aligned(256))) unsigned char icd_zero_page[256];   // zero-initialised, one per TU
 

@@ -669,15 +669,10 @@ int launch_reduce(const GemmK& k, hipStream_t st) {
 template <int MODE, bool TRANS, int WM, int NSTAGE, bool XATTN = false>
 int launch(const GemmK& k, int batch, hipStream_t st) {
     constexpr int smem = NSTAGE * (WM * 64 + BN) * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<MODE, TRANS, WM, NSTAGE, XATTN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    dim3 grid(k.nbm * k.nbn, k.ksplit, batch);
-    hipLaunchKernelGGL((gemm_kernel<MODE, TRANS, WM, NSTAGE, XATTN>), grid, dim3(WM * 128), smem, st, k);
-    ICD_CHECK_LAUNCH("icd_gemm");
+    static std::atomic<unsigned long long> armed{0};
+    const int rc = icd_launch_lds(armed, "icd_gemm", &gemm_kernel<MODE, TRANS, WM, NSTAGE, XATTN>, dim3(k.nbm * k.nbn, k.ksplit, batch), dim3(WM * 128),
+                                  smem, st, k);
+    if (rc != ICD_OK) return rc;
     if (k.ksplit > 1) return launch_reduce(k, st);
     return ICD_OK;
 }

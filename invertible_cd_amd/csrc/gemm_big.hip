@@ -9,9 +9,11 @@
 //   * serves every layer with N % 256 == 0: the GEGLU projections (N = 8C) and the 1280-channel convs / Linears.
 //   * 2 LDS stages of 64 KiB.  The barrier of k-tile t+1 is taken in the shadow of the last sub-step's 8 queued MFMAs of
 //     k-tile t: wait vmcnt -> s_barrier -> issue the loads of t+2 -> prefetch the first fragments of t+1.
-//   * Loader, swizzle, epilogue and split-K are those of gemm.hip (same LDS image, same epilogue arithmetic).
+//   * Swizzle, epilogue and split-K are those of gemm.hip (same LDS image, same epilogue arithmetic); the dense loader too.  The conv A
+//     gather is gemm_conv_gather.h (the ping-pong tiles, gemm_pp.hip and gemm_pp320.hip, keep copies of their own).
 #include <type_traits>
 #include "gemm_common.h"
+#include "gemm_conv_gather.h"
 #include "gemm_epilogue.h"
 
 using namespace icd_gemm_detail;
@@ -199,11 +201,6 @@ __device__ __forceinline__ void xattn_epilogue_big(const GemmK& p, f32x16 (&acc)
     if constexpr (TM == 3) tiles(I1{}, I2{});
 }
 
-#ifndef ICD_CONV_CHUNK_MAJOR
-#define ICD_CONV_CHUNK_MAJOR 1
-#endif
-constexpr bool CONV_CHUNK_MAJOR = ICD_CONV_CHUNK_MAJOR != 0;       // K order of the conv tiles (see the loader)
-
 constexpr int enc_vmcnt(int n) { return ((n >> 4) << 14) | 0x0F70 | (n & 15); }
 
 // LNS (round 5): the instantiation that may compute LayerNorm statistics in its main loop (p.ln_stats_w).  As a run-time flag in ONE kernel
@@ -245,28 +242,19 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
     // ---- loader state (see gemm.hip: biased pointers, zero-page parking, one M0 per group of 4 chunks) ----------
     const int lrow = l >> 3, pchunk = l & 7;
     const int Cin = p.C0 + p.C1;
-    const int ntaps = p.ksize * p.ksize, pad = (p.flags & ICD_GEMM_PAD_HI) ? 0 : p.ksize >> 1;
+    const ConvGeom geom(p);
     const int ktaps = (int)(p.tapmap >> 60);     // taps iterated: ntaps, or 4 of the 9 (phase form of the upsampling conv: tap u -> tap_base + (u & 1) + 3 (u >> 1))
-    const int Hu = p.Hin << p.upsample, Wu = p.Win << p.upsample;
     const int k_begin = kt_begin * BK;
 
-    // conv A operand (round 4): LDS-DMA through a BUFFER descriptor (buffer_load_dwordx4 ... offen lds) instead of 64-bit global pointers.
-    // Per 16-B chunk the loader keeps a 32-bit byte offset of the row's tap-(0,0) pixel in the source being read and the complement of a
-    // 9-bit tap-validity mask (zero padding, rows >= M); per k-tile the offset to issue is (that offset + a wave-uniform tap / channel term)
-    // with bit 31 set where the tap is invalid - out of the descriptor's range (sources < 2 GiB on this path, checked on the host), so the
-    // DMA writes zeros: 3 VALU issues per chunk and k-tile (add, bfe, lshl_or), no zero-page pointer select, no per-tap recompute of
-    // (y, x, pixel), two registers per chunk less than round 3's loader.  That economy is what makes the CHUNK-major K order affordable
-    // (k-tile = chunk * taps + tap: the nine taps of a 64-channel chunk back to back, the nine uses of a [rows + halo] x 64-channel slab inside
-    // nine consecutive k-tiles: L2 hits instead of 9 fabric reads per line; weights stay tap-major in memory), see profiles/r04_conv_korder.txt.
+    // conv A operand (round 4): LDS-DMA through a BUFFER descriptor, per-chunk (a_pix, a_off, a_nmsk) and the CHUNK-major K order
+    // (k-tile = chunk * taps + tap; weights stay tap-major in memory) - gemm_conv_gather.h, measured in profiles/r04_conv_korder.txt
     const half_t* a_ptr[NAJ]; int a_inc[NAJ];    // dense (MODE 0)
-    unsigned a_off[NAJ], a_nmsk[NAJ], a_voff[NAJ];   // conv: see above; a_nmsk bits 0..8 = tap INVALID, bits 9 / 10 = row / column parity (upsample)
-    int a_pix[NAJ];                              // conv: source pixel index of tap (0, 0) (a_off for the second concat source derives from it)
+    unsigned a_off[NAJ], a_nmsk[NAJ], a_voff[NAJ];   // conv: a_voff = the offsets to issue
+    int a_pix[NAJ];
     const half_t* w_ptr[NWJ]; int w_inc[NWJ];
-    const int cpt = MODE == 1 ? Cin / BK : 1;    // k-tiles per tap
-    int u_tap, u_c;
-    if (CONV_CHUNK_MAJOR && MODE == 1) { const int ch = kt_begin / ktaps; u_tap = kt_begin - ch * ktaps; u_c = ch * BK; }
-    else { u_tap = MODE == 1 ? kt_begin / cpt : 0; u_c = MODE == 1 ? (kt_begin - u_tap * cpt) * BK : 0; }
-    const int w_k0 = (CONV_CHUNK_MAJOR && MODE == 1) ? u_tap * Cin + u_c : k_begin;
+    ConvKPos pos = {0, 0};
+    if (MODE == 1) pos.start(kt_begin, ktaps);
+    const int w_k0 = MODE == 1 ? pos.w_k(Cin) : k_begin;
 #pragma unroll
     for (int j = 0; j < NAJ; ++j) {
         const int r = (wv * NAJ + j) * 8 + lrow;
@@ -274,24 +262,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
         const int m = m0 + r;
         const int boff = (j & 3) * 512;          // bias for the instruction's immediate offset (halves)
         a_ptr[j] = zero - boff; a_inc[j] = 0; a_pix[j] = 0; a_nmsk[j] = 0x1ff; a_off[j] = 0; a_voff[j] = 0x80000000u;
-        if (m < m_lim) {
-            if (MODE == 0) {
-                a_ptr[j] = p.a0 + (long long)m * p.lda + k_begin + lc * 8 - boff; a_inc[j] = BK;
-            } else {
-                const int hw = p.Hout * p.Wout;
-                const int b = m / hw, rem = m - b * hw;
-                const int y = rem / p.Wout, x = rem - y * p.Wout;
-                const int yu0 = y * p.stride - pad, xu0 = x * p.stride - pad;
-                unsigned nm = 0x1ff;
-                for (int t = 0; t < ntaps; ++t) {
-                    const int dy = ntaps == 9 ? t / 3 : 0, dx = ntaps == 9 ? t - dy * 3 : 0;
-                    if ((unsigned)(yu0 + dy) < (unsigned)Hu && (unsigned)(xu0 + dx) < (unsigned)Wu) nm &= ~(1u << t);
-                }
-                if (p.upsample) nm |= ((unsigned)(yu0 & 1) << 9) | ((unsigned)(xu0 & 1) << 10);
-                a_nmsk[j] = nm;
-                a_pix[j] = b * p.Hin * p.Win + (yu0 >> p.upsample) * p.Win + (xu0 >> p.upsample);
-            }
-        }
+        if (MODE == 1) conv_row(p, geom, m, m_lim, a_pix[j], a_nmsk[j]);
+        else if (m < m_lim) { a_ptr[j] = p.a0 + (long long)m * p.lda + k_begin + lc * 8 - boff; a_inc[j] = BK; }
     }
 #pragma unroll
     for (int j = 0; j < NWJ; ++j) {
@@ -301,11 +273,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
         const bool ok = n < p.Nw;
         const int boff = (j & 3) * 512;
         w_ptr[j] = ok ? p.w + (long long)n * p.ldw + w_k0 + lc * 8 - boff : zero - boff;
-        w_inc[j] = ok ? ((CONV_CHUNK_MAJOR && MODE == 1) ? -1 : BK) : 0;       // chunk-major: a mask for the per-k-tile step
+        w_inc[j] = ok ? (MODE == 1 ? -1 : BK) : 0;       // conv: a mask for the per-k-tile step (w_step)
     }
     // buffer descriptors of the (up to two) conv sources: base, bytes, raw 32-bit offsets, bounds-checked
-    const int conv_nb = MODE == 1 ? (p.M + p.Hout * p.Wout - 1) / (p.Hout * p.Wout) : 0;
-    const unsigned src_px = (unsigned)conv_nb * (unsigned)(p.Hin * p.Win);
+    const unsigned src_px = MODE == 1 ? conv_src_px(p) : 0u;
     (void)src_px;
     // (the descriptor type exists in the device pass only: the host pass of hipcc, which needs nothing but the kernel's stub, would drop
     //  the whole template silently - stubs undefined at load time - if it met it)
@@ -320,37 +291,20 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
         for (int j = 0; j < NAJ; ++j) {
             const int r = (wv * NAJ + j) * 8 + lrow;
             const int lc = pchunk ^ ((r >> 1) & 7);
-            a_off[j] = ((unsigned)a_pix[j] * (unsigned)Cs + (unsigned)(lc * 8)) * 2u;
+            a_off[j] = conv_src_off(a_pix[j], Cs, lc);
         }
         u_first = first;
     };
     int w_step = BK;
     // offsets of the NEXT k-tile to be issued, computed right after the loads of the current one are in flight
     auto conv_next = [&]() {
-        const int t3 = (int)((p.tapmap >> (4 * u_tap)) & 15u);       // iterated tap -> tap of the 3 x 3 geometry (wave-uniform: one 64-bit scalar shift)
-        const int dy = (t3 * 11) >> 5, dx = t3 - dy * 3;             // (0, 0) for a 1 x 1 conv
-        const bool first = u_c < p.C0;
-        if (first != u_first) set_source(first);
-        const int Cs = first ? p.C0 : p.C1, cc = first ? u_c : u_c - p.C0;
-        const unsigned s_tap = (unsigned)(((dy * p.Win + dx) * Cs + cc) * 2);        // wave-uniform (no upsample)
+        const ConvKTile k = pos.decode(p);
+        if (k.first != u_first) set_source(k.first);
 #pragma unroll
-        for (int j = 0; j < NAJ; ++j) {
-            unsigned off = a_off[j] + s_tap;
-            if (p.upsample) {
-                const int doff = (int)((((a_nmsk[j] >> 9) & 1) + dy) >> 1) * p.Win + (int)((((a_nmsk[j] >> 10) & 1) + dx) >> 1);
-                off = a_off[j] + (unsigned)((doff * Cs + cc) * 2);
-            }
-            a_voff[j] = off | (__builtin_amdgcn_ubfe(a_nmsk[j], (unsigned)t3, 1u) << 31);
-        }
-        if (CONV_CHUNK_MAJOR) {                                      // k-tile -> (chunk, tap)
-            w_step = Cin;
-            if (++u_tap == ktaps) { u_tap = 0; u_c += BK; w_step = BK - (ktaps - 1) * Cin; }
-        } else {                                                     // k-tile -> (tap, chunk)
-            u_c += BK;
-            if (u_c == Cin) { u_c = 0; ++u_tap; }
-        }
+        for (int j = 0; j < NAJ; ++j) a_voff[j] = conv_chunk_off(p, k, a_off[j], a_nmsk[j]);
+        w_step = pos.step(ktaps) ? BK - (ktaps - 1) * Cin : Cin;     // weights are tap-major: next tap, or back to tap 0 of the next chunk
     };
-    if (MODE == 1) { set_source(u_c < p.C0); conv_next(); }          // offsets of the first k-tile
+    if (MODE == 1) { set_source(pos.u_c < p.C0); conv_next(); }      // offsets of the first k-tile
 
     const int wave_a = __builtin_amdgcn_readfirstlane(wv * NAJ * 1024);
     const int wave_w = __builtin_amdgcn_readfirstlane(A_BYTES + wv * NWJ * 1024);
@@ -388,7 +342,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
             else if ((j & 3) == 1) GLDS(w_ptr[j], base, 1024);
             else if ((j & 3) == 2) GLDS(w_ptr[j], base, 2048);
             else GLDS(w_ptr[j], base, 3072);
-            w_ptr[j] += (CONV_CHUNK_MAJOR && MODE == 1) ? (w_step & w_inc[j]) : w_inc[j];
+            w_ptr[j] += MODE == 1 ? (w_step & w_inc[j]) : w_inc[j];
         }
         if (MODE == 1) conv_next();
     };
@@ -417,10 +371,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
             }
     }
     f16x8 af[2][TM], wf[2][TN];               // set 1 is unused (and dead-code eliminated) without DBUF
-    // LayerNorm statistics of the A rows, in-kernel (p.ln_stats_w): the WN waves of a tile row see every element of their rows go
-    // by as MFMA operands (K = the LayerNorm width) and share the work - wave wn sums the k sub-steps s4 with s4 % WN == wn;
-    // lane (lr, lh) covers the k-columns it holds, v_dot2_f32_f16 with fp32 accumulate.  (All of it on the waves of column 0 made
-    // them the block's critical path: +10 % on a 40-n-tile GEGLU launch.)
+    // LayerNorm statistics of the A rows, in-kernel (p.ln_stats_w, gemm_common.h): wave wn sums the k sub-steps s4 with s4 % WN == wn.
+    // (All of it on the waves of column 0 made them the block's critical path: +10 % on a 40-n-tile GEGLU launch.)
     const bool stat_on = LNS && MODE == 0 && p.ln_stats_w != nullptr;
     float st_s[TM], st_q[TM];
 #pragma unroll
@@ -434,18 +386,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
     };
     auto mfmas = [&](auto set_tag, auto sub_tag) {
         constexpr int SET = decltype(set_tag)::value, S4 = decltype(sub_tag)::value;
-        if (stat_on && (S4 % WN) == wn) {        // (slipping the dots in between the MFMAs makes hipcc spill hundreds of registers)
-            typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-            const h2 one = {(_Float16)1.f, (_Float16)1.f};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const h2 v = {af[SET][i][2 * e], af[SET][i][2 * e + 1]};
-                    st_s[i] = __builtin_amdgcn_fdot2(v, one, st_s[i], false);
-                    st_q[i] = __builtin_amdgcn_fdot2(v, v, st_q[i], false);
-                }
-        }
+        // (slipping the dots in between the MFMAs makes hipcc spill hundreds of registers)
+        if (stat_on && (S4 % WN) == wn) ln_row_sums<TM>([&](int i) -> const f16x8& { return af[SET][i]; }, st_s, st_q);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -507,52 +449,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
 
     if (tl && tid == 0) tl[5] = __builtin_amdgcn_s_memtime();        // shader-clock ticks of the main loop (clock = ticks / time)
     const float* ln_lds = nullptr;
-    if (stat_on) {
-        // per-wave partial sums -> LDS (behind the epilogue's staging patches), summed over the WN waves of the tile row in a fixed
-        // order; (mean, rstd) of the block's rows -> an LDS table for the epilogue, and to memory by n-tile 0 (a later GEMM
-        // normalised by the same LayerNorm reads them there)
-        float* table = reinterpret_cast<float*>(smem + LN_TABLE_OFF);
-        float* parts = table + 2 * BM;                                     // [WN][BM][2]
-        __syncthreads();                         // every wave is done with the stage buffers
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const float s_ = st_s[i] + __shfl_xor(st_s[i], 32), q_ = st_q[i] + __shfl_xor(st_q[i], 32);
-            if (lh == 0) *reinterpret_cast<f32x2*>(parts + 2 * (wn * BM + (wm * TM + i) * 32 + lr)) = (f32x2){s_, q_};
-        }
-        __syncthreads();
-        if (wn == 0 && lh == 0) {
-            const float inv_k = 1.f / (float)p.K;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int row = (wm * TM + i) * 32 + lr;
-                float s_ = 0.f, q_ = 0.f;
-#pragma unroll
-                for (int w = 0; w < WN; ++w) {
-                    const f32x2 v = *reinterpret_cast<const f32x2*>(parts + 2 * (w * BM + row));
-                    s_ += v[0]; q_ += v[1];
-                }
-                const float mean = s_ * inv_k;
-                float var = fmaxf(q_ * inv_k - mean * mean, 0.f);
-                // One-pass variance: E[x^2] - mean^2 loses ~ (1 + mean^2 / var) x 1e-6 of relative accuracy.  Rows whose offset
-                // dominates their spread (|mean| > 4 sigma: not seen on zero-centred transformer activations, but a row is a row)
-                // take the exact second pass instead - sum (x - mean)^2 in fp32 over the row, which the tile just streamed through L2.
-                if (mean * mean > 16.f * var && m0 + row < m_lim) {
-                    const half_t* ar = p.a0 + (long long)(m0 + row) * p.lda;
-                    float acc2 = 0.f;
-                    for (int kk = 0; kk < p.K; kk += 8) {
-                        const f16x8 v = *reinterpret_cast<const f16x8*>(ar + kk);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) { const float dlt = (float)v[e] - mean; acc2 = __builtin_fmaf(dlt, dlt, acc2); }
-                    }
-                    var = acc2 * inv_k;
-                }
-                const float rstd = rsqrtf(var + p.ln_eps);
-                *reinterpret_cast<f32x2*>(table + 2 * row) = (f32x2){mean, rstd};
-                if (nt == 0 && m0 + row < m_lim) *reinterpret_cast<f32x2*>(p.ln_stats_w + 2 * (long long)(m0 + row)) = (f32x2){mean, rstd};
-            }
-        }
-        ln_lds = table;                          // indexed by row - m0 (the epilogue's own barrier publishes it)
-    }
+    if (stat_on) ln_lds = ln_stats_finish<TM, WN, BM>(p, st_s, st_q, smem + LN_TABLE_OFF, wm, wn, lr, lh, m0, m_lim, nt);
     // ---- epilogue (gemm_epilogue.h): per-wave LDS patches, no block-wide slabs -----------------------------------------
     // (since the fast path is specialised by operand mix, the 256 x 320 conv tile - 160 accumulators + the im2col loader state -
     //  fits it too: FAST_OK stays a template switch for experiments)
@@ -571,23 +468,13 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_big_kernel(GemmK p) {
     }
 }
 
-// LNS (round 5): the instantiation that may compute LayerNorm statistics in its main loop (p.ln_stats_w).  As a run-time flag in ONE kernel
-// the statistics code put a branch and a join into every k sub-step of every dense launch, and at each join the waitcnt pass drained ALL
-// outstanding ds_reads (s_waitcnt lgkmcnt(0)) - including the fragments just requested for the NEXT sub-step, i.e. the register double
-// buffering was dead in every dense GEMM (8 full drains per k-tile pair against 4 in the conv kernels, which never had the branch).
 template <int MODE, int WM, int WN, int TM, int TN, bool XATTN = false, bool CARRY = false, bool LNS = false>
 int launch_one(const GemmK& k, hipStream_t st) {
     constexpr int smem0 = 2 * (WM * TM * 32 + WN * TN * 32) * 128;
     constexpr int smem = XATTN && XA_SMEM > smem0 ? XA_SMEM : smem0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big_kernel<MODE, WM, WN, TM, TN, XATTN, CARRY, LNS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_big_kernel<MODE, WM, WN, TM, TN, XATTN, CARRY, LNS>), dim3(k.nbm * k.nbn, k.ksplit, 1), dim3(WM * WN * 64), smem, st, k);
-    ICD_CHECK_LAUNCH("icd_gemm(big tile)");
-    return ICD_OK;
+    static std::atomic<unsigned long long> armed{0};
+    return icd_launch_lds(armed, "icd_gemm(big tile)", &gemm_big_kernel<MODE, WM, WN, TM, TN, XATTN, CARRY, LNS>, dim3(k.nbm * k.nbn, k.ksplit, 1),
+                          dim3(WM * WN * 64), smem, st, k);
 }
 
 }  // namespace

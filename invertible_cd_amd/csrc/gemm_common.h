@@ -100,6 +100,73 @@ __device__ __forceinline__ void ln_correct8(float (&v)[8], const float* ln_stats
     }
 }
 
+// LayerNorm statistics of the A rows taken in the main loop of the big tiles (p.ln_stats_w; gemm_big.hip, gemm_pp.hip, gemm_pp320.hip).
+// The WN waves of a tile row see every element of their rows go by as MFMA operands (K = the LayerNorm width) and share the work:
+// lane (lr, lh) covers the k-columns it holds, v_dot2_f32_f16 with fp32 accumulate.  ln_row_sums: the N row tiles of one k sub-step
+// (frag(i) = the A fragment of row tile i) into the running sum / sum of squares; each kernel chooses the sub-steps of a wave and where in its loop.
+template <int N, typename F>
+__device__ __forceinline__ void ln_row_sums(F frag, float* s, float* q) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 one = {(_Float16)1.f, (_Float16)1.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const f16x8& a = frag(i);
+            const h2 v = {a[2 * e], a[2 * e + 1]};
+            s[i] = __builtin_amdgcn_fdot2(v, one, s[i], false);
+            q[i] = __builtin_amdgcn_fdot2(v, v, q[i], false);
+        }
+}
+// ... and the finish after the loop: per-wave partial sums -> LDS (`lds`: past the epilogue's staging patches, (1 + WN) * BM * 8 bytes),
+// summed over the WN waves of the tile row in a fixed order; (mean, rstd) of the block's rows -> the table at `lds` for the epilogue
+// (indexed by row - m0; the epilogue's own barrier publishes it), and to memory by n-tile 0 (a later GEMM normalised by the same
+// LayerNorm reads them there).  Returns the table.
+template <int TM, int WN, int BM>
+__device__ __forceinline__ const float* ln_stats_finish(const GemmK& p, const float (&st_s)[TM], const float (&st_q)[TM], unsigned char* lds,
+                                                        int wm, int wn, int lr, int lh, int m0, int m_lim, int nt) {
+    float* table = reinterpret_cast<float*>(lds);
+    float* parts = table + 2 * BM;                                         // [WN][BM][2]
+    __syncthreads();                             // every wave is done with the stage buffers
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const float s_ = st_s[i] + __shfl_xor(st_s[i], 32), q_ = st_q[i] + __shfl_xor(st_q[i], 32);
+        if (lh == 0) *reinterpret_cast<f32x2*>(parts + 2 * (wn * BM + (wm * TM + i) * 32 + lr)) = (f32x2){s_, q_};
+    }
+    __syncthreads();
+    if (wn == 0 && lh == 0) {
+        const float inv_k = 1.f / (float)p.K;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = (wm * TM + i) * 32 + lr;
+            float s_ = 0.f, q_ = 0.f;
+#pragma unroll
+            for (int w = 0; w < WN; ++w) {
+                const f32x2 v = *reinterpret_cast<const f32x2*>(parts + 2 * (w * BM + row));
+                s_ += v[0]; q_ += v[1];
+            }
+            const float mean = s_ * inv_k;
+            float var = fmaxf(q_ * inv_k - mean * mean, 0.f);
+            // One-pass variance: E[x^2] - mean^2 loses ~ (1 + mean^2 / var) x 1e-6 of relative accuracy.  Rows whose offset
+            // dominates their spread (|mean| > 4 sigma: not seen on zero-centred transformer activations, but a row is a row)
+            // take the exact second pass instead - sum (x - mean)^2 in fp32 over the row, which the tile just streamed through L2.
+            if (mean * mean > 16.f * var && m0 + row < m_lim) {
+                const half_t* ar = p.a0 + (long long)(m0 + row) * p.lda;
+                float acc2 = 0.f;
+                for (int kk = 0; kk < p.K; kk += 8) {
+                    const f16x8 v = *reinterpret_cast<const f16x8*>(ar + kk);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { const float dlt = (float)v[e] - mean; acc2 = __builtin_fmaf(dlt, dlt, acc2); }
+                }
+                var = acc2 * inv_k;
+            }
+            const float rstd = rsqrtf(var + p.ln_eps);
+            *reinterpret_cast<f32x2*>(table + 2 * row) = (f32x2){mean, rstd};
+            if (nt == 0 && m0 + row < m_lim) *reinterpret_cast<f32x2*>(p.ln_stats_w + 2 * (long long)(m0 + row)) = (f32x2){mean, rstd};
+        }
+    }
+    return table;
+}
 
 // Error carry of the residual stream (icd_gemm_desc.resid_carry / out_carry): value = fp16 + 2^-14 * bf8_e5m2.  |v - fp16(v)| is at most
 // half an ulp of the fp16 value, so with the fixed scale 2^14 the carry of any |v| < 2^13 sits inside the bf8 range (e5m2: 32 binades)

@@ -64,7 +64,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmK p) {
     const int k_begin = kt_begin * BK;
 
     // ---- loader: per-lane byte offsets of the 2 x 4 half-tile chunks (slot order W0, A0, W1, A1), bit 31 = outside the operand ----
-    // MODE 1 (implicit-GEMM conv, gemm_big.hip's loader in this kernel's staging order): the A offsets change with every k-tile - tap and
+    // MODE 1 (implicit-GEMM conv, the gather of gemm_conv_gather.h in this kernel's staging order, kept here as this kernel's own copy: through
+    // the shared helpers the conv instantiations ran 1 - 4 % slower on the M = 8192 layers, profiles/r13_gemm_gather_bench.txt): the A offsets change with every k-tile - tap and
     // 64-channel chunk of the (up to two) NHWC sources, K order chunk-major (k-tile = chunk * taps + tap), weights tap-major in memory;
     // per chunk the lane keeps the byte offset of its row's tap-(0,0) pixel and the complement of a 9-bit tap-validity mask.
     unsigned voff[4][2];
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmK p) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     f16x8 af[2][4], wf[2][4];
-    // LayerNorm statistics of the A rows from the operand fragments (p.ln_stats_w, see gemm_big.hip): wave wn sums k sub-step s4 == wn of
+    // LayerNorm statistics of the A rows from the operand fragments (p.ln_stats_w, see gemm_common.h): wave wn sums k sub-step s4 == wn of
     // its rows; here the sums are taken at the head of the load section that follows the A half's matrix sections (the fragments are
     // still in registers, the wave has nothing else to issue while its partner holds the matrix pipe)
     const bool stat_on = LNS && MODE == 0 && p.ln_stats_w != nullptr;
@@ -218,20 +219,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmK p) {
         constexpr int HA = decltype(ha_tag)::value;
         if constexpr (LNS) {
             if (stat_on) {
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                const h2 one = {(_Float16)1.f, (_Float16)1.f};
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    if (s4 != wn) continue;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int ii = 0; ii < (HA == 0 ? 2 : NA1); ++ii) {
-                            const h2 v = {af[ii][s4][2 * e], af[ii][s4][2 * e + 1]};
-                            st_s[2 * HA + ii] = __builtin_amdgcn_fdot2(v, one, st_s[2 * HA + ii], false);
-                            st_q[2 * HA + ii] = __builtin_amdgcn_fdot2(v, v, st_q[2 * HA + ii], false);
-                        }
-                }
+                for (int s4 = 0; s4 < 4; ++s4)
+                    if (s4 == wn) ln_row_sums<(HA == 0 ? 2 : NA1)>([&](int i) -> const f16x8& { return af[i][s4]; }, st_s + 2 * HA, st_q + 2 * HA);
             }
         }
     };
@@ -409,48 +399,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmK p) {
 
     const float* ln_lds = nullptr;
     if constexpr (LNS) {
-        if (stat_on) {                               // as gemm_big.hip: per-wave sums -> LDS, (mean, rstd) table for the epilogue, stored by n-tile 0
-            constexpr int LN_TABLE_OFF = 96 * 1024;
-            static_assert(LN_TABLE_OFF + 5 * PP_BM * 8 <= PP_SMEM, "LayerNorm table does not fit");
-            float* table = reinterpret_cast<float*>(smem + LN_TABLE_OFF);
-            float* parts = table + 2 * PP_BM;        // [4][BM][2]
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const float s_ = st_s[i] + __shfl_xor(st_s[i], 32), q_ = st_q[i] + __shfl_xor(st_q[i], 32);
-                if (lh == 0) *reinterpret_cast<f32x2*>(parts + 2 * (wn * PP_BM + (wm * TM + i) * 32 + lr)) = (f32x2){s_, q_};
-            }
-            __syncthreads();
-            if (wn == 0 && lh == 0) {
-                const float inv_k = 1.f / (float)p.K;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int row = (wm * TM + i) * 32 + lr;
-                    float s_ = 0.f, q_ = 0.f;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const f32x2 v = *reinterpret_cast<const f32x2*>(parts + 2 * (w * PP_BM + row));
-                        s_ += v[0]; q_ += v[1];
-                    }
-                    const float mean = s_ * inv_k;
-                    float var = fmaxf(q_ * inv_k - mean * mean, 0.f);
-                    if (mean * mean > 16.f * var && m0 + row < p.M) {      // offset-dominated row: exact second pass (gemm_big.hip)
-                        const half_t* ar = p.a0 + (long long)(m0 + row) * p.lda;
-                        float acc2 = 0.f;
-                        for (int kk = 0; kk < p.K; kk += 8) {
-                            const f16x8 v = *reinterpret_cast<const f16x8*>(ar + kk);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) { const float dlt = (float)v[e] - mean; acc2 = __builtin_fmaf(dlt, dlt, acc2); }
-                        }
-                        var = acc2 * inv_k;
-                    }
-                    const float rstd = rsqrtf(var + p.ln_eps);
-                    *reinterpret_cast<f32x2*>(table + 2 * row) = (f32x2){mean, rstd};
-                    if (nt == 0 && m0 + row < p.M) *reinterpret_cast<f32x2*>(p.ln_stats_w + 2 * (long long)(m0 + row)) = (f32x2){mean, rstd};
-                }
-            }
-            ln_lds = table;
-        }
+        constexpr int LN_TABLE_OFF = 96 * 1024;      // past the epilogue's staging patches
+        static_assert(LN_TABLE_OFF + 5 * PP_BM * 8 <= PP_SMEM, "LayerNorm table does not fit");
+        if (stat_on) ln_lds = ln_stats_finish<TM, 4, PP_BM>(p, st_s, st_q, smem + LN_TABLE_OFF, wm, wn, lr, lh, m0, p.M, nt);
     }
     wave_epilogue<TM, 2, true, CARRY>(p, acc, smem, wv, wm, wn, l, m0, n0, split, tl, ln_lds);
     if (tl) {
@@ -461,14 +412,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmK p) {
 
 template <int MODE, bool CARRY, int V = 2, bool LNS = false, int TM = 4>
 int launch_pp_one(const GemmK& k, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<MODE, CARRY, V, LNS, TM>), hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_pp_kernel<MODE, CARRY, V, LNS, TM>), dim3(k.nbm * k.nbn, k.ksplit, 1), dim3(512), PP_SMEM, st, k);
-    ICD_CHECK_LAUNCH("icd_gemm(ping-pong tile)");
-    return ICD_OK;
+    static std::atomic<unsigned long long> armed{0};
+    return icd_launch_lds(armed, "icd_gemm(ping-pong tile)", &gemm_pp_kernel<MODE, CARRY, V, LNS, TM>, dim3(k.nbm * k.nbn, k.ksplit, 1), dim3(512),
+                          PP_SMEM, st, k);
 }
 
 }  // namespace

@@ -48,7 +48,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp320_kernel(GemmK p) {
     const int nk = min(nk_total, kt_begin + p.kt_per_split) - kt_begin;
     const int k_begin = kt_begin * BK;
 
-    // ---- loader: per-lane byte offsets (bit 31 = outside the operand); MODE 1: gemm_pp.hip's conv loader ----
+    // ---- loader: per-lane byte offsets (bit 31 = outside the operand); MODE 1: the conv gather of gemm_conv_gather.h, kept here as this kernel's
+    //      own copy - at 256 VGPRs the conv instantiations spill more registers through the shared helpers (profiles/r13_gemm_gather_isa.txt) ----
     unsigned voff_a[2][2], voff_w[5];
     unsigned a_off[2][2], a_nmsk[2][2];
     int a_pix[2][2];
@@ -199,23 +200,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pp320_kernel(GemmK p) {
     float st_s[2], st_q[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) { st_s[i] = 0.f; st_q[i] = 0.f; }
-    auto stats = [&]() {                         // wave wn sums the k sub-steps s4 with s4 % 2 == wn of its rows (gemm_big.hip)
+    auto stats = [&]() {                         // wave wn sums the k sub-steps s4 with s4 % 2 == wn of its rows (gemm_common.h)
         if constexpr (LNS) {
             if (stat_on) {
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                const h2 one = {(_Float16)1.f, (_Float16)1.f};
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    if ((s4 & 1) != wn) continue;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const h2 v = {af[i][s4][2 * e], af[i][s4][2 * e + 1]};
-                            st_s[i] = __builtin_amdgcn_fdot2(v, one, st_s[i], false);
-                            st_q[i] = __builtin_amdgcn_fdot2(v, v, st_q[i], false);
-                        }
-                }
+                for (int s4 = 0; s4 < 4; ++s4)
+                    if ((s4 & 1) == wn) ln_row_sums<2>([&](int i) -> const f16x8& { return af[i][s4]; }, st_s, st_q);
             }
         }
     };
@@ -310,44 +300,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp320_kernel(GemmK p) {
 
     const float* ln_lds = nullptr;
     if constexpr (LNS) {
-        if (stat_on) {                               // as gemm_big.hip: per-wave sums -> LDS, (mean, rstd) table for the epilogue, stored by n-tile 0
-            constexpr int LN_TABLE_OFF = 96 * 1024;
-            static_assert(LN_TABLE_OFF + 3 * P3_BM * 8 <= P3_SMEM, "LayerNorm table does not fit");
-            float* table = reinterpret_cast<float*>(smem + LN_TABLE_OFF);
-            float* parts = table + 2 * P3_BM;        // [2][BM][2]
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float s_ = st_s[i] + __shfl_xor(st_s[i], 32), q_ = st_q[i] + __shfl_xor(st_q[i], 32);
-                if (lh == 0) *reinterpret_cast<f32x2*>(parts + 2 * (wn * P3_BM + (wm * 2 + i) * 32 + lr)) = (f32x2){s_, q_};
-            }
-            __syncthreads();
-            if (wn == 0 && lh == 0) {
-                const float inv_k = 1.f / (float)p.K;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int row = (wm * 2 + i) * 32 + lr;
-                    const f32x2 v0 = *reinterpret_cast<const f32x2*>(parts + 2 * row), v1 = *reinterpret_cast<const f32x2*>(parts + 2 * (P3_BM + row));
-                    const float s_ = v0[0] + v1[0], q_ = v0[1] + v1[1];
-                    const float mean = s_ * inv_k;
-                    float var = fmaxf(q_ * inv_k - mean * mean, 0.f);
-                    if (mean * mean > 16.f * var && m0 + row < p.M) {      // offset-dominated row: exact second pass (gemm_big.hip)
-                        const half_t* ar = p.a0 + (long long)(m0 + row) * p.lda;
-                        float acc2 = 0.f;
-                        for (int kk = 0; kk < p.K; kk += 8) {
-                            const f16x8 v = *reinterpret_cast<const f16x8*>(ar + kk);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) { const float dlt = (float)v[e] - mean; acc2 = __builtin_fmaf(dlt, dlt, acc2); }
-                        }
-                        var = acc2 * inv_k;
-                    }
-                    const float rstd = rsqrtf(var + p.ln_eps);
-                    *reinterpret_cast<f32x2*>(table + 2 * row) = (f32x2){mean, rstd};
-                    if (nt == 0 && m0 + row < p.M) *reinterpret_cast<f32x2*>(p.ln_stats_w + 2 * (long long)(m0 + row)) = (f32x2){mean, rstd};
-                }
-            }
-            ln_lds = table;
-        }
+        constexpr int LN_TABLE_OFF = 96 * 1024;      // past the epilogue's staging patches
+        static_assert(LN_TABLE_OFF + 3 * P3_BM * 8 <= P3_SMEM, "LayerNorm table does not fit");
+        if (stat_on) ln_lds = ln_stats_finish<2, 2, P3_BM>(p, st_s, st_q, smem + LN_TABLE_OFF, wm, wn, lr, lh, m0, p.M, nt);
     }
     wave_epilogue<2, 5, true, CARRY>(p, acc, smem, wv, wm, wn, l, m0, n0, split, tl, ln_lds);
     if (tl) {
@@ -358,14 +313,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp320_kernel(GemmK p) {
 
 template <int MODE, bool CARRY, bool LNS = false>
 int launch_pp320_one(const GemmK& k, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp320_kernel<MODE, CARRY, LNS>), hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_pp320_kernel<MODE, CARRY, LNS>), dim3(k.nbm * k.nbn, k.ksplit, 1), dim3(512), P3_SMEM, st, k);
-    ICD_CHECK_LAUNCH("icd_gemm(ping-pong 256 x 320 tile)");
-    return ICD_OK;
+    static std::atomic<unsigned long long> armed{0};
+    return icd_launch_lds(armed, "icd_gemm(ping-pong 256 x 320 tile)", &gemm_pp320_kernel<MODE, CARRY, LNS>, dim3(k.nbm * k.nbn, k.ksplit, 1),
+                          dim3(512), P3_SMEM, st, k);
 }
 
 }  // namespace

@@ -308,6 +308,102 @@ def test_conv_odd_and_non_square_maps(cfg):
     assert rel_l2(out, to_nhwc(ref)) < TOL
 
 
+def _conv_plan(c, flags):
+    """icd_gemm_plan of the launch ops.conv3x3 makes for conv case `c` (one phase of the phase form if c["phases"]), with the split-K
+    workspace attached as ops.conv3x3 attaches it: without one the planner never splits."""
+    import ctypes as C
+    from invertible_cd_amd import _lib
+    up, stride, ksize = c.get("up", False), c.get("stride", 1), c.get("ksize", 3)
+    Hu, Wu = (c["H"] * 2, c["W"] * 2) if up else (c["H"], c["W"])
+    Ho, Wo = (Hu + stride - 1) // stride, (Wu + stride - 1) // stride
+    Cin = c["C0"] + c.get("C1", 0)
+    d = _lib.GemmDesc()
+    buf = torch.empty(8, device="cuda")
+    d.a0 = d.w = d.out = buf.data_ptr()
+    d.a1 = buf.data_ptr() if c.get("C1") else None
+    d.M, d.N, d.Nw, d.K = c["B"] * Ho * Wo, 1280, 1280, (4 if c.get("phases") else ksize * ksize) * Cin
+    if c.get("phases"):
+        d.conv_tap_base, d.conv_ktaps, d.out_remap_w, d.out_remap_c = 0, 4, c["W"], 0
+    d.lda, d.ldw, d.ldo, d.rows_per_sample = 0, d.K, 1280, Ho * Wo
+    d.mode, d.C0, d.C1 = 1, c["C0"], c.get("C1", 0)
+    d.Hin, d.Win, d.Hout, d.Wout, d.ksize, d.stride, d.upsample = c["H"], c["W"], Ho, Wo, ksize, stride, int(up)
+    d.batch, d.zdiv, d.alpha, d.flags = 1, 1, 1.0, flags | (_lib.ICD_GEMM_PAD_HI if c.get("pad_hi") else 0)
+    ws = _ops()._splitk_ws(d, "cuda")               # (kept alive until the plan is made)
+    info = _lib.GemmPlanInfo()
+    _lib.check(_lib.load().icd_gemm_plan(C.byref(d), C.byref(info)), "icd_gemm_plan")
+    del ws
+    return info
+
+
+# Co = 1280 (divisible by 256 and 320), Cin a multiple of 64; B = 3 on maps of about 13 x 9: M = 351, a ragged last m-tile on every tile height
+CONV_TILE_CASES = [
+    dict(name="3x3", B=3, H=13, W=9, C0=128),
+    dict(name="3x3 two sources", B=3, H=13, W=9, C0=64, C1=64),                 # the source switches inside K
+    dict(name="stride 2", B=3, H=26, W=18, C0=128, stride=2),
+    dict(name="stride 2 pad_hi", B=3, H=26, W=18, C0=128, stride=2, pad_hi=True),
+    dict(name="upsample of an odd map", B=3, H=7, W=5, C0=128, up=True),
+    dict(name="phase form", B=3, H=13, W=9, C0=128, phases=True),               # conv_ktaps = 4, out_remap_w; against the upsample form too
+    dict(name="1x1", B=3, H=13, W=9, C0=128, ksize=1),
+    dict(name="split K", B=4, H=8, W=8, C0=1280, split=True),                    # ksplit > 1: kt_begin != 0 enters the chunk / tap start
+]
+
+
+def conv_tile_case_outputs(c, cfg_i):
+    """Inputs, torch reference and the output of conv case `c` on forced big-tile configuration cfg_i: (out, ref, plan[, 3x3 upsample form])."""
+    ops = _ops()
+    from invertible_cd_amd.unet import upsample_phase_weights
+    B, H, W, C0, C1, Co, ksize = c["B"], c["H"], c["W"], c["C0"], c.get("C1", 0), 1280, c.get("ksize", 3)
+    Cin, flag = C0 + C1, (cfg_i + 1) << 24
+    x, x2 = r16(B, C0, H, W, seed=465), (r16(B, C1, H, W, seed=466) if C1 else None)
+    w = r16(Co, Cin, ksize, ksize, seed=467, scale=(ksize * ksize * Cin) ** -0.5)
+    bias = torch.randn(Co, generator=torch.Generator().manual_seed(468)) * 0.1
+    if "ref" not in c:                                # one reference per case, shared by the seven configurations
+        xin = x.float() if x2 is None else torch.cat([x.float(), x2.float()], 1)
+        if c.get("up") or c.get("phases"):
+            xin = F.interpolate(xin, scale_factor=2.0, mode="nearest")
+        if c.get("pad_hi"):
+            c["ref"] = to_nhwc(F.conv2d(F.pad(xin, (0, 1, 0, 1)), w.float(), bias, stride=2))
+        else:
+            c["ref"] = to_nhwc(F.conv2d(xin, w.float(), bias, stride=c.get("stride", 1), padding=ksize >> 1))
+    plan = _conv_plan(c, flag)
+    xn = to_nhwc(x).cuda()
+    if c.get("phases"):
+        out = torch.empty(B * 4 * H * W, Co, device="cuda", dtype=torch.float16)
+        for ph, wp in enumerate(upsample_phase_weights(w)):
+            ops.conv3x3(xn, B, H, W, wp.reshape(Co, -1).half().contiguous().cuda(), bias.cuda(), phase=ph, out=out, debug_flags=flag)
+        old = ops.conv3x3(xn, B, H, W, ops.pack_conv_weight(w).cuda(), bias.cuda(), upsample=True, debug_flags=flag)
+        return out, c["ref"], plan, old
+    out = ops.conv3x3(xn, B, H, W, ops.pack_conv_weight(w).cuda(), bias.cuda(), x2=None if x2 is None else to_nhwc(x2).cuda(), stride=c.get("stride", 1),
+                      upsample=c.get("up", False), pad_hi=c.get("pad_hi", False), ksize=ksize, debug_flags=flag)
+    return out, c["ref"], plan
+
+
+@pytest.mark.parametrize("case", CONV_TILE_CASES, ids=lambda c: c["name"].replace(" ", "_"))
+def test_conv_variants_on_every_big_tile_configuration(case):
+    """Every conv variant of the A gather (gemm_conv_gather.h and its copies in the ping-pong tiles) forced on each of the seven big-tile configurations
+    (ICD_GEMM_TUNE_BIG_CFG): the plan reports the forced tile, the output matches torch's fp32 conv on the fp16 operands, and a ping-pong
+    tile gives the bits of the lockstep tile of its shape (configurations 4 / 0, 5 / 1, 6 / 2) wherever the two plans split K alike."""
+    from invertible_cd_amd import _lib
+    tiles = [(256, 256), (256, 320), (192, 256), (128, 320), (256, 256), (256, 320), (192, 256)]
+    outs, plans = [], []
+    for cfg_i in range(7):
+        got = conv_tile_case_outputs(case, cfg_i)
+        out, ref, plan = got[:3]
+        e = rel_l2(out, ref)
+        print(f"[conv {case['name']} cfg {cfg_i}] tile {plan.tile_m}x{plan.tile_n} ksplit {plan.ksplit} rel-L2 {e:.3e}")
+        assert plan.kernel == 1 and (plan.tile_m, plan.tile_n) == tiles[cfg_i]
+        assert e < TOL
+        if len(got) == 4:                             # the 3 x 3 form with the upsampling in its loader, on the same tile
+            assert rel_l2(got[3], ref) < TOL and rel_l2(out, got[3].float().cpu()) < TOL
+        if case.get("split"):
+            assert plan.ksplit > 1
+        outs.append(out)
+        plans.append(plan.ksplit)
+    for pp, lock in ((4, 0), (5, 1), (6, 2)):
+        if plans[pp] == plans[lock]:
+            assert torch.equal(outs[pp], outs[lock]), f"configuration {pp} against {lock}"
+
+
 @pytest.mark.parametrize("M,N,K,flags", [(8192, 1280, 1280, 0),                                    # planner: 192 x 256 tile, fast variant R32 + O32
                                          (4096, 512, 512, 0x100000 | (1 << 24)),                     # forced 256 x 256
                                          (4096, 640, 640, 0x100000 | (2 << 24)),                     # forced 256 x 320 (general epilogue)
