@@ -8,6 +8,7 @@
 namespace {
 
 constexpr int GN_THREADS = 512;
+constexpr int GN_MAX_GROUPS = 32;     // groupnorm_run refuses more: the apply kernels keep (mean, rstd) per group in static LDS
 
 // pixels per statistics block: about 768 blocks per launch (3 per CU) but never fewer than 64 pixels per block
 // (round-3 sweep, profiles/r03_gn_sweep.txt: 768 statistics blocks per launch beat 1536 by 2-13 % on the C = 320 levels and tie
@@ -21,69 +22,7 @@ __host__ __device__ inline int gn_pix_per_split(int B, int HW, int tgt = 768) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// GroupNorm pass 1: per (sample, pixel-slab) partial (sum, sumsq) per group.  Thread -> fixed 8-channel chunk.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const half_t* __restrict__ x0, int C0,
-                                                               const half_t* __restrict__ x1, int C1, int HW,
-                                                               int groups, int pix_per_split, float* __restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float* part = reinterpret_cast<float*>(smem_raw);          // [rows_per_iter][C][2]
-    const int C = C0 + C1, nchunk = C >> 3;
-    const int rpi = GN_THREADS / nchunk;
-    const int tid = threadIdx.x;
-    const int chunk = tid % nchunk, rsub = tid / nchunk;
-    const int b = blockIdx.y, sp = blockIdx.x, nsplit = gridDim.x;
-    const int p_begin = sp * pix_per_split;
-    const int p_end = min(HW, p_begin + pix_per_split);
-    float s[8], q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-    if (rsub < rpi) {
-        const int ch = chunk * 8;
-        const bool first = ch < C0;
-        const half_t* base = first ? x0 + (long long)b * HW * C0 + ch : x1 + (long long)b * HW * C1 + (ch - C0);
-        const int cs = first ? C0 : C1;
-        // 4 independent 16-B loads in flight per thread per iteration (HBM-bound: keep the memory pipe full)
-        int p = p_begin + rsub;
-        for (; p + 3 * rpi < p_end; p += 4 * rpi) {
-            f16x8 v0 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)p * cs));
-            f16x8 v1 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + rpi) * cs));
-            f16x8 v2 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + 2 * rpi) * cs));
-            f16x8 v3 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + 3 * rpi) * cs));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f0 = (float)v0[e], f1 = (float)v1[e], f2 = (float)v2[e], f3 = (float)v3[e];
-                s[e] += (f0 + f1) + (f2 + f3);
-                q[e] += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
-            }
-        }
-        for (; p < p_end; p += rpi) {
-            f16x8 v = *reinterpret_cast<const f16x8*>(base + (long long)p * cs);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s[e] += f; q[e] += f * f; }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            part[((rsub * C) + ch + e) * 2 + 0] = s[e];
-            part[((rsub * C) + ch + e) * 2 + 1] = q[e];
-        }
-    }
-    __syncthreads();
-    if (tid < groups) {
-        const int cpg = C / groups;
-        float ss = 0.f, qq = 0.f;
-        for (int r = 0; r < rpi; ++r)
-            for (int c = 0; c < cpg; ++c) {
-                ss += part[((r * C) + tid * cpg + c) * 2 + 0];
-                qq += part[((r * C) + tid * cpg + c) * 2 + 1];
-            }
-        float* o = ws + (((long long)b * nsplit + sp) * groups + tid) * 2;
-        o[0] = ss; o[1] = qq;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// GroupNorm pass 2: finish the statistics (fixed order), normalise, affine, optional SiLU, write one NHWC tensor.
+// GroupNorm, fp16 NHWC input [x0 (C0) | x1 (C1)].  Thread -> fixed 8-channel chunk, rows GN_THREADS / nchunk apart.
 // ---------------------------------------------------------------------------------------------------------------
 // CARRY (round 5): the inputs are tensors of the residual stream that travel with their bf8 error carry (value = fp16 + 2^-14 * bf8,
 // gemm_common.h) - the normalisation reads fp16 + carry (the statistics pass keeps reading the fp16 part: a mean over thousands of
@@ -101,64 +40,113 @@ __device__ __forceinline__ void gn_carry8(float (&f)[8], const u32x2 w) {
     f[4] = c2[0] * k; f[5] = c2[1] * k; f[6] = c3[0] * k; f[7] = c3[1] * k;
 }
 
-template <bool CARRY>
-__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const half_t* __restrict__ x0, int C0,
-                                                               const half_t* __restrict__ x1, int C1, int HW,
-                                                               int groups, int nsplit, int pix_per_block,
-                                                               const float* __restrict__ ws,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float eps, int silu,
-                                                               half_t* __restrict__ out, GnCarry cy) {
-    __shared__ float s_mean[64], s_rstd[64];
-    const int C = C0 + C1, nchunk = C >> 3;
-    const int rpi = GN_THREADS / nchunk;
-    const int tid = threadIdx.x, b = blockIdx.y;
-    {   // finish the statistics: 16 lanes per group walk the partials (fixed order -> reproducible), DPP tree on top
-        const int g = tid >> 4, j = tid & 15;
-        float ss = 0.f, qq = 0.f;
-        if (g < groups)
-            for (int sp = j; sp < nsplit; sp += 16) {
-                const float* o = ws + (((long long)b * nsplit + sp) * groups + g) * 2;
-                ss += o[0]; qq += o[1];
-            }
-        ss = group_sum<16>(ss); qq = group_sum<16>(qq);
-        if (g < groups && j == 0) {
-            const float n = (float)HW * (float)(C / groups);
-            const float mean = ss / n;
-            const float var = fmaxf(qq / n - mean * mean, 0.f);
-            s_mean[g] = mean;
-            s_rstd[g] = rsqrtf(var + eps);
+// lo = fp16(2^-14 * carry) of 8 carry bytes
+__device__ __forceinline__ f16x8 carry_lo8(const u32x2 w) {
+    float cf[8];
+    gn_carry8(cf, w);
+    f16x8 lo;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) lo[e] = (half_t)cf[e];
+    return lo;
+}
+
+// A thread's 8-channel chunk `ch` of sample b in the concat: which source, its pixel 0 there and its row stride; once gn_source_carry
+// has run also the chunk's carry bytes (same [pixel][channel] layout as the fp16 tensor, one byte per element; null for a source
+// without a carry) and its places in the aux rows.
+struct GnSrc {
+    bool first; const half_t* base; int cs;
+    const unsigned char* cbase; half_t* aux_lo; half_t* aux_hi; int ld_aux;
+};
+
+__device__ __forceinline__ GnSrc gn_source(const half_t* x0, int C0, const half_t* x1, int C1, int HW, int b, int ch) {
+    GnSrc s;
+    s.first = ch < C0;
+    s.base = s.first ? x0 + (long long)b * HW * C0 + ch : x1 + (long long)b * HW * C1 + (ch - C0);
+    s.cs = s.first ? C0 : C1;
+    s.cbase = nullptr; s.aux_lo = nullptr; s.aux_hi = nullptr; s.ld_aux = 0;
+    return s;
+}
+
+__device__ __forceinline__ void gn_source_carry(GnSrc& s, const GnCarry& cy, int C0, int C1, int HW, int b, int ch) {
+    const unsigned char* csrc = s.first ? cy.c0 : cy.c1;
+    if (csrc) s.cbase = csrc + (long long)b * HW * s.cs + (s.first ? ch : ch - C0);
+    s.ld_aux = cy.ld_aux;
+    if (cy.aux) {
+        half_t* arow = cy.aux + (long long)b * HW * cy.ld_aux;
+        s.aux_lo = arow + C1 + ch;                              // [x1 | lo0 | lo1]: lo of concat channel ch sits at C1 + ch
+        if (!s.first) s.aux_hi = arow + (ch - C0);
+    }
+}
+
+// Per-channel (sum, sumsq) of pixels p, p + rpi, ... < p_end of one chunk, left in the thread's row of the LDS partials.
+// NT: the tensor is not read again soon (the streaming pass); plain loads where the second read is meant to hit L2.
+template <bool NT>
+__device__ __forceinline__ void gn_accumulate(const half_t* base, int cs, int p, int p_end, int rpi, float* part_row) {
+    float s[8], q[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+    auto ld = [&](int pp) {
+        const f16x8* a = reinterpret_cast<const f16x8*>(base + (long long)pp * cs);
+        return NT ? __builtin_nontemporal_load(a) : *a;
+    };
+    // 4 independent 16-B loads in flight per thread per iteration (HBM-bound: keep the memory pipe full)
+    for (; p + 3 * rpi < p_end; p += 4 * rpi) {
+        const f16x8 v0 = ld(p), v1 = ld(p + rpi), v2 = ld(p + 2 * rpi), v3 = ld(p + 3 * rpi);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float f0 = (float)v0[e], f1 = (float)v1[e], f2 = (float)v2[e], f3 = (float)v3[e];
+            s[e] += (f0 + f1) + (f2 + f3);
+            q[e] += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
         }
     }
-    __syncthreads();
-    const int chunk = tid % nchunk, rsub = tid / nchunk;
-    if (rsub >= rpi) return;
-    const int ch = chunk * 8, cpg = C / groups;
-    float sc[8], sh[8];
+    for (; p < p_end; p += rpi) {
+        const f16x8 v = *reinterpret_cast<const f16x8*>(base + (long long)p * cs);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s[e] += f; q[e] += f * f; }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { part_row[e * 2] = s[e]; part_row[e * 2 + 1] = q[e]; }
+}
+
+// LDS partials [rpi][C][2] -> (sum, sumsq) of group g (cpg channels), fixed order: row slot outer, channel inner
+__device__ __forceinline__ void gn_reduce_group(const float* part, int C, int rpi, int cpg, int g, float* o) {
+    float ss = 0.f, qq = 0.f;
+    for (int r = 0; r < rpi; ++r)
+        for (int c = 0; c < cpg; ++c) {
+            ss += part[((r * C) + g * cpg + c) * 2 + 0];
+            qq += part[((r * C) + g * cpg + c) * 2 + 1];
+        }
+    o[0] = ss; o[1] = qq;
+}
+
+// Workspace partials [B][nsplit][groups][2] -> (sum, sumsq) of group tid / 16 of sample b: its 16 lanes walk the partials (fixed
+// order -> reproducible), DPP tree on top.  Every thread of the block calls it; every lane of a group gets the sums.
+__device__ __forceinline__ void gn_finish_sums(const float* ws, int b, int nsplit, int groups, float& ss, float& qq) {
+    const int g = threadIdx.x >> 4, j = threadIdx.x & 15;
+    ss = 0.f; qq = 0.f;
+    if (g < groups)
+        for (int sp = j; sp < nsplit; sp += 16) {
+            const float* o = ws + (((long long)b * nsplit + sp) * groups + g) * 2;
+            ss += o[0]; qq += o[1];
+        }
+    ss = group_sum<16>(ss); qq = group_sum<16>(qq);
+}
+
+// y = x * sc + sh for channels ch .. ch + 7 from the groups' (mean, rstd) pairs in LDS; cl = ch counted from stat's first group
+__device__ __forceinline__ void gn_scale_shift(const float* stat, int cl, int cpg, const float* gamma, const float* beta, int ch,
+                                               float (&sc)[8], float (&sh)[8]) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int g = (ch + e) / cpg;
-        sc[e] = s_rstd[g] * gamma[ch + e];
-        sh[e] = beta[ch + e] - s_mean[g] * sc[e];
+        const int g = (cl + e) / cpg;
+        sc[e] = stat[g * 2 + 1] * gamma[ch + e];
+        sh[e] = beta[ch + e] - stat[g * 2] * sc[e];
     }
-    const bool first = ch < C0;
-    const half_t* base = first ? x0 + (long long)b * HW * C0 + ch : x1 + (long long)b * HW * C1 + (ch - C0);
-    const int cs = first ? C0 : C1;
-    half_t* ob = out + (long long)b * HW * C + ch;
-    const int p_begin = blockIdx.x * pix_per_block;
-    const int p_end = min(HW, p_begin + pix_per_block);
-    // carry bytes of this thread's 8 channels (same [pixel][channel] layout as the fp16 tensor, one byte per element)
-    const unsigned char* cbase = nullptr;
-    half_t* aux_lo = nullptr; half_t* aux_hi = nullptr;
-    if (CARRY) {
-        const unsigned char* csrc = first ? cy.c0 : cy.c1;
-        if (csrc) cbase = csrc + (long long)b * HW * cs + (first ? ch : ch - C0);
-        if (cy.aux) {
-            half_t* arow = cy.aux + (long long)b * HW * cy.ld_aux;
-            aux_lo = arow + (C1 ? C1 : 0) + ch;                     // [x1 | lo0 | lo1]: lo of concat channel ch sits at C1 + ch
-            if (!first) aux_hi = arow + (ch - C0);
-        }
-    }
+}
+
+// Normalise, affine, optional SiLU of pixels p, p + rpi, ... < p_end of one chunk into ob (row stride C); with CARRY also the aux rows.
+template <bool CARRY, bool NT>
+__device__ __forceinline__ void gn_apply_rows(const float (&sc)[8], const float (&sh)[8], const GnSrc& src, half_t* ob, int C, int p,
+                                              int p_end, int rpi, int silu) {
     auto norm8 = [&](const f16x8& v, const u32x2 w, long long prow) {
         f16x8 o;
         float cf[8];
@@ -171,34 +159,92 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const half_t* __re
             if (silu) f = silu_f(f);
             o[e] = (half_t)f;
         }
-        if (CARRY && aux_lo) {
-            f16x8 lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) lo[e] = (half_t)cf[e];
-            *reinterpret_cast<f16x8*>(aux_lo + prow * cy.ld_aux) = lo;
-            if (aux_hi) *reinterpret_cast<f16x8*>(aux_hi + prow * cy.ld_aux) = v;
+        if (CARRY && src.aux_lo) {
+            *reinterpret_cast<f16x8*>(src.aux_lo + prow * src.ld_aux) = carry_lo8(w);
+            if (src.aux_hi) *reinterpret_cast<f16x8*>(src.aux_hi + prow * src.ld_aux) = v;
         }
         return o;
     };
+    auto ld = [&](int pp) {
+        const f16x8* a = reinterpret_cast<const f16x8*>(src.base + (long long)pp * src.cs);
+        return NT ? __builtin_nontemporal_load(a) : *a;
+    };
     auto ldc = [&](long long prow) {
         u32x2 w = {0u, 0u};
-        if (CARRY && cbase) w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(cbase + prow * cs));
+        if (CARRY && src.cbase) {
+            const u32x2* a = reinterpret_cast<const u32x2*>(src.cbase + prow * src.cs);
+            w = NT ? __builtin_nontemporal_load(a) : *a;
+        }
         return w;
     };
-    int p = p_begin + rsub;
     for (; p + 3 * rpi < p_end; p += 4 * rpi) {          // 4 loads in flight per thread
-        f16x8 v0 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)p * cs));
-        f16x8 v1 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + rpi) * cs));
-        f16x8 v2 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + 2 * rpi) * cs));
-        f16x8 v3 = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(base + (long long)(p + 3 * rpi) * cs));
+        const f16x8 v0 = ld(p), v1 = ld(p + rpi), v2 = ld(p + 2 * rpi), v3 = ld(p + 3 * rpi);
         const u32x2 w0 = ldc(p), w1 = ldc(p + rpi), w2 = ldc(p + 2 * rpi), w3 = ldc(p + 3 * rpi);
         *reinterpret_cast<f16x8*>(ob + (long long)p * C) = norm8(v0, w0, p);
         *reinterpret_cast<f16x8*>(ob + (long long)(p + rpi) * C) = norm8(v1, w1, p + rpi);
         *reinterpret_cast<f16x8*>(ob + (long long)(p + 2 * rpi) * C) = norm8(v2, w2, p + 2 * rpi);
         *reinterpret_cast<f16x8*>(ob + (long long)(p + 3 * rpi) * C) = norm8(v3, w3, p + 3 * rpi);
     }
-    for (; p < p_end; p += rpi)
-        *reinterpret_cast<f16x8*>(ob + (long long)p * C) = norm8(*reinterpret_cast<const f16x8*>(base + (long long)p * cs), ldc(p), p);
+    for (; p < p_end; p += rpi) {
+        const f16x8 v = *reinterpret_cast<const f16x8*>(src.base + (long long)p * src.cs);
+        *reinterpret_cast<f16x8*>(ob + (long long)p * C) = norm8(v, ldc(p), p);
+    }
+}
+
+// GroupNorm pass 1: per (sample, pixel-slab) partial (sum, sumsq) per group.
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const half_t* __restrict__ x0, int C0,
+                                                               const half_t* __restrict__ x1, int C1, int HW,
+                                                               int groups, int pix_per_split, float* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float* part = reinterpret_cast<float*>(smem_raw);          // [rows_per_iter][C][2]
+    const int C = C0 + C1, nchunk = C >> 3;
+    const int rpi = GN_THREADS / nchunk;
+    const int tid = threadIdx.x;
+    const int chunk = tid % nchunk, rsub = tid / nchunk;
+    const int b = blockIdx.y, sp = blockIdx.x, nsplit = gridDim.x;
+    const int p_begin = sp * pix_per_split;
+    const int p_end = min(HW, p_begin + pix_per_split);
+    if (rsub < rpi) {
+        const int ch = chunk * 8;
+        const GnSrc src = gn_source(x0, C0, x1, C1, HW, b, ch);
+        gn_accumulate<true>(src.base, src.cs, p_begin + rsub, p_end, rpi, part + (rsub * C + ch) * 2);
+    }
+    __syncthreads();
+    if (tid < groups) gn_reduce_group(part, C, rpi, C / groups, tid, ws + (((long long)b * nsplit + sp) * groups + tid) * 2);
+}
+
+// GroupNorm pass 2: finish the statistics (fixed order), normalise, affine, optional SiLU, write one NHWC tensor.
+template <bool CARRY>
+__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const half_t* __restrict__ x0, int C0,
+                                                               const half_t* __restrict__ x1, int C1, int HW,
+                                                               int groups, int nsplit, int pix_per_block,
+                                                               const float* __restrict__ ws,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps, int silu,
+                                                               half_t* __restrict__ out, GnCarry cy) {
+    __shared__ float stat[GN_MAX_GROUPS * 2];                   // [groups][2] mean, rstd
+    const int C = C0 + C1, nchunk = C >> 3;
+    const int rpi = GN_THREADS / nchunk;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    float ss, qq;
+    gn_finish_sums(ws, b, nsplit, groups, ss, qq);
+    if (const int g = tid >> 4; g < groups && (tid & 15) == 0) {
+        const float n = (float)HW * (float)(C / groups);
+        const float mean = ss / n;
+        stat[g * 2] = mean;
+        stat[g * 2 + 1] = rsqrtf(fmaxf(qq / n - mean * mean, 0.f) + eps);
+    }
+    __syncthreads();
+    const int chunk = tid % nchunk, rsub = tid / nchunk;
+    if (rsub >= rpi) return;
+    const int ch = chunk * 8;
+    float sc[8], sh[8];
+    gn_scale_shift(stat, ch, C / groups, gamma, beta, ch, sc, sh);
+    GnSrc src = gn_source(x0, C0, x1, C1, HW, b, ch);
+    if (CARRY) gn_source_carry(src, cy, C0, C1, HW, b, ch);
+    const int p_begin = blockIdx.x * pix_per_block;
+    gn_apply_rows<CARRY, true>(sc, sh, src, out + (long long)b * HW * C + ch, C, p_begin + rsub, min(HW, p_begin + pix_per_block), rpi,
+                               silu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -224,37 +270,8 @@ __global__ __launch_bounds__(GN_THREADS) void gn_small_kernel(const half_t* __re
     const int chunk = tid % nch, rsub = tid / nch;
     const bool live = rsub < rpi;
     const int ch = c_lo + chunk * 8;
-    const bool first = ch < C0;
-    const half_t* base = first ? x0 + (long long)b * HW * C0 + ch : x1 + (long long)b * HW * C1 + (ch - C0);
-    const int cs = first ? C0 : C1;
-    float s[8], q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-    if (live) {
-        int p = rsub;
-        for (; p + 3 * rpi < HW; p += 4 * rpi) {
-            f16x8 v0 = *reinterpret_cast<const f16x8*>(base + (long long)p * cs);
-            f16x8 v1 = *reinterpret_cast<const f16x8*>(base + (long long)(p + rpi) * cs);
-            f16x8 v2 = *reinterpret_cast<const f16x8*>(base + (long long)(p + 2 * rpi) * cs);
-            f16x8 v3 = *reinterpret_cast<const f16x8*>(base + (long long)(p + 3 * rpi) * cs);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f0 = (float)v0[e], f1 = (float)v1[e], f2 = (float)v2[e], f3 = (float)v3[e];
-                s[e] += (f0 + f1) + (f2 + f3);
-                q[e] += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
-            }
-        }
-        for (; p < HW; p += rpi) {
-            f16x8 v = *reinterpret_cast<const f16x8*>(base + (long long)p * cs);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s[e] += f; q[e] += f * f; }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            part[((rsub * CB) + chunk * 8 + e) * 2 + 0] = s[e];
-            part[((rsub * CB) + chunk * 8 + e) * 2 + 1] = q[e];
-        }
-    }
+    GnSrc src = gn_source(x0, C0, x1, C1, HW, b, ch);
+    if (live) gn_accumulate<false>(src.base, src.cs, rsub, HW, rpi, part + (rsub * CB + chunk * 8) * 2);
     __syncthreads();
     if (tid < CB) {                                             // per-channel totals over the row slots (fixed order)
         float ss = 0.f, qq = 0.f;
@@ -273,64 +290,10 @@ __global__ __launch_bounds__(GN_THREADS) void gn_small_kernel(const half_t* __re
     __syncthreads();
     if (!live) return;
     float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int g = (chunk * 8 + e) / cpg;
-        sc[e] = stat[g * 2 + 1] * gamma[ch + e];
-        sh[e] = beta[ch + e] - stat[g * 2] * sc[e];
-    }
-    half_t* ob = out + (long long)b * HW * C + ch;
-    const unsigned char* cbase = nullptr;
-    half_t* aux_lo = nullptr; half_t* aux_hi = nullptr;
-    if (CARRY) {
-        const unsigned char* csrc = first ? cy.c0 : cy.c1;
-        if (csrc) cbase = csrc + (long long)b * HW * cs + (first ? ch : ch - C0);
-        if (cy.aux) {
-            half_t* arow = cy.aux + (long long)b * HW * cy.ld_aux;
-            aux_lo = arow + C1 + ch;
-            if (!first) aux_hi = arow + (ch - C0);
-        }
-    }
-    auto norm8 = [&](const f16x8& v, const u32x2 w, long long prow) {
-        f16x8 o;
-        float cf[8];
-        if (CARRY) gn_carry8(cf, w);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float f = (float)v[e];
-            if (CARRY) f += cf[e];
-            f = f * sc[e] + sh[e];
-            if (silu) f = silu_f(f);
-            o[e] = (half_t)f;
-        }
-        if (CARRY && aux_lo) {
-            f16x8 lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) lo[e] = (half_t)cf[e];
-            *reinterpret_cast<f16x8*>(aux_lo + prow * cy.ld_aux) = lo;
-            if (aux_hi) *reinterpret_cast<f16x8*>(aux_hi + prow * cy.ld_aux) = v;
-        }
-        return o;
-    };
-    auto ldc = [&](long long prow) {
-        u32x2 w = {0u, 0u};
-        if (CARRY && cbase) w = *reinterpret_cast<const u32x2*>(cbase + prow * cs);
-        return w;
-    };
-    int p = rsub;
-    for (; p + 3 * rpi < HW; p += 4 * rpi) {
-        f16x8 v0 = *reinterpret_cast<const f16x8*>(base + (long long)p * cs);
-        f16x8 v1 = *reinterpret_cast<const f16x8*>(base + (long long)(p + rpi) * cs);
-        f16x8 v2 = *reinterpret_cast<const f16x8*>(base + (long long)(p + 2 * rpi) * cs);
-        f16x8 v3 = *reinterpret_cast<const f16x8*>(base + (long long)(p + 3 * rpi) * cs);
-        const u32x2 w0 = ldc(p), w1 = ldc(p + rpi), w2 = ldc(p + 2 * rpi), w3 = ldc(p + 3 * rpi);
-        *reinterpret_cast<f16x8*>(ob + (long long)p * C) = norm8(v0, w0, p);
-        *reinterpret_cast<f16x8*>(ob + (long long)(p + rpi) * C) = norm8(v1, w1, p + rpi);
-        *reinterpret_cast<f16x8*>(ob + (long long)(p + 2 * rpi) * C) = norm8(v2, w2, p + 2 * rpi);
-        *reinterpret_cast<f16x8*>(ob + (long long)(p + 3 * rpi) * C) = norm8(v3, w3, p + 3 * rpi);
-    }
-    for (; p < HW; p += rpi)
-        *reinterpret_cast<f16x8*>(ob + (long long)p * C) = norm8(*reinterpret_cast<const f16x8*>(base + (long long)p * cs), ldc(p), p);
+    gn_scale_shift(stat, chunk * 8, cpg, gamma, beta, ch, sc, sh);
+    // (behind the barriers on purpose: set up before the statistics pass the carry and aux pointers stay live across it, 77 -> 80 VGPRs)
+    if (CARRY) gn_source_carry(src, cy, C0, C1, HW, b, ch);
+    gn_apply_rows<CARRY, false>(sc, sh, src, out + (long long)b * HW * C + ch, C, rsub, HW, rpi, silu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -367,14 +330,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_f32_kernel(const float* _
         for (int e = 0; e < 4; ++e) { part[((rsub * C) + chunk * 4 + e) * 2] = s[e]; part[((rsub * C) + chunk * 4 + e) * 2 + 1] = q[e]; }
     }
     __syncthreads();
-    if (tid < groups) {
-        const int cpg = C / groups;
-        float ss = 0.f, qq = 0.f;
-        for (int r = 0; r < rpi; ++r)
-            for (int c = 0; c < cpg; ++c) { ss += part[((r * C) + tid * cpg + c) * 2]; qq += part[((r * C) + tid * cpg + c) * 2 + 1]; }
-        float* o = ws + (((long long)b * nsplit + sp) * groups + tid) * 2;
-        o[0] = ss; o[1] = qq;
-    }
+    if (tid < groups) gn_reduce_group(part, C, rpi, C / groups, tid, ws + (((long long)b * nsplit + sp) * groups + tid) * 2);
 }
 
 __device__ __forceinline__ void split_store4(half_t* row, int C, int c, const float (&v)[4]) {
@@ -393,21 +349,13 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_split_kernel(const float*
     __shared__ float s_mean[64], s_rstd[64];
     const int nchunk = C >> 2, rpi = GN_THREADS / nchunk;
     const int tid = threadIdx.x, b = blockIdx.y;
-    {
-        const int g = tid >> 4, j = tid & 15;
-        float ss = 0.f, qq = 0.f;
-        if (g < groups)
-            for (int sp = j; sp < nsplit; sp += 16) {
-                const float* o = ws + (((long long)b * nsplit + sp) * groups + g) * 2;
-                ss += o[0]; qq += o[1];
-            }
-        ss = group_sum<16>(ss); qq = group_sum<16>(qq);
-        if (g < groups && j == 0) {
-            const float n = (float)HW * (float)(C / groups);
-            const float dm = ss / n;                             // mean of (x - pivot), see gn_stats_f32_kernel
-            s_mean[g] = x[(long long)b * HW * C + g * (C / groups)] + dm;
-            s_rstd[g] = rsqrtf(fmaxf(qq / n - dm * dm, 0.f) + eps);
-        }
+    float ss, qq;
+    gn_finish_sums(ws, b, nsplit, groups, ss, qq);
+    if (const int g = tid >> 4; g < groups && (tid & 15) == 0) {
+        const float n = (float)HW * (float)(C / groups);
+        const float dm = ss / n;                                 // mean of (x - pivot), see gn_stats_f32_kernel
+        s_mean[g] = x[(long long)b * HW * C + g * (C / groups)] + dm;
+        s_rstd[g] = rsqrtf(fmaxf(qq / n - dm * dm, 0.f) + eps);
     }
     __syncthreads();
     const int chunk = tid % nchunk, rsub = tid / nchunk;
@@ -454,11 +402,15 @@ __global__ __launch_bounds__(256) void split_cast_kernel(const float* __restrict
 
 // ---------------------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per token row, row kept in registers (C <= 2048), exact two-pass mean / variance.
+// STATS: write (mean, rstd) per row to `stats` instead of the normalised rows - the LayerNorm itself is then applied
+// inside the consuming GEMM (gamma folded into its weights, mean / rstd as a rank-1 epilogue correction; icd_gemm_desc
+// ln_stats / ln_colsum): the normalised tensor is never written or re-read.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool STATS>
 __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict__ x, long long rows, int C,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float eps,
-                                                         half_t* __restrict__ out) {
+                                                         half_t* __restrict__ out, float* __restrict__ stats) {
     const int l = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -486,6 +438,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
         }
     }
     const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+    if (STATS) {
+        if (l == 0) *reinterpret_cast<f32x2*>(stats + row * 2) = (f32x2){mean, rstd};
+        return;
+    }
     half_t* orow = out + row * C;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -512,9 +468,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int LN_ITERS = 4;
 
-// STATS: write (mean, rstd) per row to `stats` instead of the normalised rows - the LayerNorm itself is then applied
-// inside the consuming GEMM (gamma folded into its weights, mean / rstd as a rank-1 epilogue correction; icd_gemm_desc
-// ln_stats / ln_colsum): the normalised tensor is never written or re-read.
 template <int LPR, int CPL, bool STATS = false>
 __global__ __launch_bounds__(256) void layernorm_multi_kernel(const half_t* __restrict__ x, long long rows, int C,
                                                                const float* __restrict__ gamma,
@@ -587,41 +540,29 @@ void launch_ln_multi(const half_t* x, long long rows, int C, const float* gamma,
                      float* stats, hipStream_t st) {
     const long long rows_per_block = 4LL * (64 / LPR) * LN_ITERS;
     const dim3 grid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
-    if (stats) hipLaunchKernelGGL((layernorm_multi_kernel<LPR, CPL, true>), grid, dim3(256), 0, st, x, rows, C, gamma, beta, eps, out, stats);
-    else hipLaunchKernelGGL((layernorm_multi_kernel<LPR, CPL, false>), grid, dim3(256), 0, st, x, rows, C, gamma, beta, eps, out, stats);
+    const auto kernel = stats ? layernorm_multi_kernel<LPR, CPL, true> : layernorm_multi_kernel<LPR, CPL, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x, rows, C, gamma, beta, eps, out, stats);
 }
 
-// generic width: one wave per row, stats only
-__global__ __launch_bounds__(256) void layernorm_stats_kernel(const half_t* __restrict__ x, long long rows, int C, float eps,
-                                                               float* __restrict__ stats) {
-    const int l = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nchunk = C >> 3;
-    const half_t* xr = x + row * C;
-    f16x8 v[4];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = l + i * 64;
-        if (c < nchunk) {
-            v[i] = *reinterpret_cast<const f16x8*>(xr + c * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum += (float)v[i][e];
-        }
-    }
-    const float mean = wave_sum(sum) / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = l + i * 64;
-        if (c < nchunk) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = (float)v[i][e] - mean; sq += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-    if (l == 0) *reinterpret_cast<f32x2*>(stats + row * 2) = (f32x2){mean, rstd};
+// icd_layernorm (stats == nullptr) and icd_layernorm_stats (gamma, beta, out unused)
+int layernorm_run(const void* x, int64_t rows, int32_t C, const float* gamma, const float* beta, float eps, void* out, float* stats,
+                  void* stream, const char* who) {
+    ICD_CHECK_ARG(x && (stats || (out && gamma && beta)), "%s: null pointer", who);
+    ICD_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 2048, "%s: C must be a multiple of 8 and <= 2048 (got %d)", who, C);
+    ICD_CHECK_ARG(rows > 0, "%s: empty input", who);
+    hipStream_t st = (hipStream_t)stream;
+    const half_t* xh = (const half_t*)x;
+    half_t* oh = (half_t*)out;
+    const int nchunk = C / 8;
+    // widths with 5 chunks per lane group (C = 320 * 2^k) take the multi-row kernel; anything else the generic one
+    if (nchunk == 40) launch_ln_multi<8, 5>(xh, rows, C, gamma, beta, eps, oh, stats, st);
+    else if (nchunk == 80) launch_ln_multi<16, 5>(xh, rows, C, gamma, beta, eps, oh, stats, st);
+    else if (nchunk == 160) launch_ln_multi<32, 5>(xh, rows, C, gamma, beta, eps, oh, stats, st);
+    else
+        hipLaunchKernelGGL(stats ? layernorm_kernel<true> : layernorm_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, xh,
+                           (long long)rows, C, gamma, beta, eps, oh, stats);
+    ICD_CHECK_LAUNCH(who);
+    return ICD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -698,7 +639,7 @@ static int groupnorm_run(const void* x0, int32_t C0, const void* c0, const void*
     const int C = C0 + C1;
     ICD_CHECK_ARG(C0 > 0 && C0 % 8 == 0 && C1 >= 0 && C1 % 8 == 0, "%s: channels must be multiples of 8", who);
     ICD_CHECK_ARG((C1 == 0) == (x1 == nullptr), "%s: x1/C1 mismatch", who);
-    ICD_CHECK_ARG(groups > 0 && groups <= 32 && C % groups == 0, "%s: bad group count %d for C=%d", who, groups, C);
+    ICD_CHECK_ARG(groups > 0 && groups <= GN_MAX_GROUPS && C % groups == 0, "%s: bad group count %d for C=%d", who, groups, C);
     ICD_CHECK_ARG(C / 8 <= GN_THREADS, "%s: C=%d too large", who, C);
     ICD_CHECK_ARG(B > 0 && HW > 0, "%s: empty input", who);
     ICD_CHECK_ARG(!(c1 && !x1), "%s: carry of an absent second source", who);
@@ -718,12 +659,8 @@ static int groupnorm_run(const void* x0, int32_t C0, const void* c0, const void*
             const int rpi_s = GN_THREADS / (cb / 8);
             const size_t smem_s = ((size_t)rpi_s * cb * 2 + (size_t)cb * 2 + (size_t)gpb * 2) * sizeof(float);
             if (smem_s <= 64 * 1024) {
-                if (carry)
-                    hipLaunchKernelGGL(gn_small_kernel<true>, dim3(groups / gpb, B), dim3(GN_THREADS), smem_s, st, (const half_t*)x0, C0,
-                                       (const half_t*)x1, C1, HW, groups, gpb, gamma, beta, eps, silu, (half_t*)out, cy);
-                else
-                    hipLaunchKernelGGL(gn_small_kernel<false>, dim3(groups / gpb, B), dim3(GN_THREADS), smem_s, st, (const half_t*)x0, C0,
-                                       (const half_t*)x1, C1, HW, groups, gpb, gamma, beta, eps, silu, (half_t*)out, cy);
+                hipLaunchKernelGGL(carry ? gn_small_kernel<true> : gn_small_kernel<false>, dim3(groups / gpb, B), dim3(GN_THREADS), smem_s, st,
+                                   (const half_t*)x0, C0, (const half_t*)x1, C1, HW, groups, gpb, gamma, beta, eps, silu, (half_t*)out, cy);
                 ICD_CHECK_LAUNCH("icd_groupnorm(small)");
                 return ICD_OK;
             }
@@ -740,12 +677,9 @@ static int groupnorm_run(const void* x0, int32_t C0, const void* c0, const void*
     // pixels per apply block: 512 - 1024 blocks per launch (same sweep: 128 at B x HW = 131072, 64 at 32768; 256 only pays on the
     // 128 x 128 maps and by < 2 %)
     const int ppb = (long long)B * HW >= 98304 ? 128 : 64;
-    if (carry)
-        hipLaunchKernelGGL(gn_apply_kernel<true>, dim3((HW + ppb - 1) / ppb, B), dim3(GN_THREADS), 0, st, (const half_t*)x0, C0,
-                           (const half_t*)x1, C1, HW, groups, nsplit, ppb, stats_ws, gamma, beta, eps, silu, (half_t*)out, cy);
-    else
-        hipLaunchKernelGGL(gn_apply_kernel<false>, dim3((HW + ppb - 1) / ppb, B), dim3(GN_THREADS), 0, st, (const half_t*)x0, C0,
-                           (const half_t*)x1, C1, HW, groups, nsplit, ppb, stats_ws, gamma, beta, eps, silu, (half_t*)out, cy);
+    hipLaunchKernelGGL(carry ? gn_apply_kernel<true> : gn_apply_kernel<false>, dim3((HW + ppb - 1) / ppb, B), dim3(GN_THREADS), 0, st,
+                       (const half_t*)x0, C0, (const half_t*)x1, C1, HW, groups, nsplit, ppb, stats_ws, gamma, beta, eps, silu, (half_t*)out,
+                       cy);
     ICD_CHECK_LAUNCH("icd_groupnorm(apply)");
     return ICD_OK;
 }
@@ -768,13 +702,7 @@ extern "C" int icd_groupnorm_carry(const void* x0, int32_t C0, const void* carry
 // tensor that no GroupNorm reads first (proj_out of a Transformer2DModel, the downsampler conv)
 __global__ __launch_bounds__(256) void carry_expand_kernel(const unsigned char* __restrict__ c, long long n8, half_t* __restrict__ lo) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-        const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(c) + i);
-        float cf[8];
-        gn_carry8(cf, w);
-        f16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)cf[e];
-        *(reinterpret_cast<f16x8*>(lo) + i) = o;
+        *(reinterpret_cast<f16x8*>(lo) + i) = carry_lo8(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(c) + i));
     }
 }
 
@@ -788,54 +716,34 @@ __global__ __launch_bounds__(256) void carry_expand2_kernel(const unsigned char*
         const int k = (int)(i - r * C8);
         const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(c) + i);
         const f16x8 h = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(hi) + i);
-        float cf[8];
-        gn_carry8(cf, w);
-        f16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)cf[e];
         f16x8* row = reinterpret_cast<f16x8*>(out) + r * (2 * C8);
-        row[k] = o;
+        row[k] = carry_lo8(w);
         row[C8 + k] = h;
     }
 }
 
+// grid-stride over the 8-element chunks
+static dim3 carry_expand_grid(long long n8) { return dim3((unsigned)std::min<long long>((n8 + 255) / 256, 4096)); }
+
 extern "C" int icd_carry_expand2(const void* carry, const void* hi, int64_t rows, int32_t C, void* out, void* stream) {
     ICD_CHECK_ARG(carry && hi && out && rows > 0 && C > 0 && C % 8 == 0, "icd_carry_expand2: null pointer or C not a multiple of 8");
-    const long long n8 = rows * (C / 8);
-    const int blocks = (int)std::min<long long>((n8 + 255) / 256, 4096);
-    hipLaunchKernelGGL(carry_expand2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)carry, (const half_t*)hi,
-                       (long long)rows, C / 8, (half_t*)out);
+    hipLaunchKernelGGL(carry_expand2_kernel, carry_expand_grid(rows * (C / 8)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)carry, (const half_t*)hi, (long long)rows, C / 8, (half_t*)out);
     ICD_CHECK_LAUNCH("icd_carry_expand2");
     return ICD_OK;
 }
 
 extern "C" int icd_carry_expand(const void* carry, int64_t n, void* lo, void* stream) {
     ICD_CHECK_ARG(carry && lo && n > 0 && n % 8 == 0, "icd_carry_expand: null pointer or element count not a multiple of 8");
-    const long long n8 = n / 8;
-    const int blocks = (int)std::min<long long>((n8 + 255) / 256, 4096);
-    hipLaunchKernelGGL(carry_expand_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)carry, n8, (half_t*)lo);
+    hipLaunchKernelGGL(carry_expand_kernel, carry_expand_grid(n / 8), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)carry,
+                       (long long)(n / 8), (half_t*)lo);
     ICD_CHECK_LAUNCH("icd_carry_expand");
     return ICD_OK;
 }
 
 extern "C" int icd_layernorm(const void* x, int64_t rows, int32_t C, const float* gamma, const float* beta, float eps,
                              void* out, void* stream) {
-    ICD_CHECK_ARG(x && out && gamma && beta, "icd_layernorm: null pointer");
-    ICD_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 2048, "icd_layernorm: C must be a multiple of 8 and <= 2048 (got %d)", C);
-    ICD_CHECK_ARG(rows > 0, "icd_layernorm: empty input");
-    hipStream_t st = (hipStream_t)stream;
-    const half_t* xh = (const half_t*)x;
-    half_t* oh = (half_t*)out;
-    const int nchunk = C / 8;
-    // widths with 5 chunks per lane group (C = 320 * 2^k) take the multi-row kernel; anything else the generic one
-    if (nchunk == 40) launch_ln_multi<8, 5>(xh, rows, C, gamma, beta, eps, oh, nullptr, st);
-    else if (nchunk == 80) launch_ln_multi<16, 5>(xh, rows, C, gamma, beta, eps, oh, nullptr, st);
-    else if (nchunk == 160) launch_ln_multi<32, 5>(xh, rows, C, gamma, beta, eps, oh, nullptr, st);
-    else
-        hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, xh, (long long)rows, C, gamma,
-                           beta, eps, oh);
-    ICD_CHECK_LAUNCH("icd_layernorm");
-    return ICD_OK;
+    return layernorm_run(x, rows, C, gamma, beta, eps, out, nullptr, stream, "icd_layernorm");
 }
 
 extern "C" int icd_groupnorm_f32_split(const float* x, int32_t C, int32_t B, int32_t HW, int32_t groups, const float* gamma,
@@ -891,18 +799,7 @@ extern "C" int icd_split_cast(const float* x, int64_t rows, int32_t C, float sca
 }
 
 extern "C" int icd_layernorm_stats(const void* x, int64_t rows, int32_t C, float eps, float* stats, void* stream) {
-    ICD_CHECK_ARG(x && stats, "icd_layernorm_stats: null pointer");
-    ICD_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 2048, "icd_layernorm_stats: C must be a multiple of 8 and <= 2048 (got %d)", C);
-    ICD_CHECK_ARG(rows > 0, "icd_layernorm_stats: empty input");
-    hipStream_t st = (hipStream_t)stream;
-    const half_t* xh = (const half_t*)x;
-    const int nchunk = C / 8;
-    if (nchunk == 40) launch_ln_multi<8, 5>(xh, rows, C, nullptr, nullptr, eps, nullptr, stats, st);
-    else if (nchunk == 80) launch_ln_multi<16, 5>(xh, rows, C, nullptr, nullptr, eps, nullptr, stats, st);
-    else if (nchunk == 160) launch_ln_multi<32, 5>(xh, rows, C, nullptr, nullptr, eps, nullptr, stats, st);
-    else hipLaunchKernelGGL(layernorm_stats_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, xh, (long long)rows, C, eps, stats);
-    ICD_CHECK_LAUNCH("icd_layernorm_stats");
-    return ICD_OK;
+    return layernorm_run(x, rows, C, nullptr, nullptr, eps, nullptr, stats, stream, "icd_layernorm_stats");
 }
 
 extern "C" int icd_softmax_rows(const float* s, int64_t rows, int32_t cols, int32_t ld_s, float scale, void* p,

@@ -557,7 +557,10 @@ def test_conv1x1_concat():
 
 @pytest.mark.parametrize("B,HW,C0,C1,silu,eps", [(2, 1024, 320, 0, True, 1e-5), (3, 64, 1280, 1280, True, 1e-5),
                                                   (2, 256, 1280, 640, True, 1e-5), (1, 4096, 320, 0, False, 1e-6),
-                                                  (2, 100, 32, 0, True, 1e-5), (1, 256, 640, 320, False, 1e-6)])
+                                                  (2, 100, 32, 0, True, 1e-5), (1, 256, 640, 320, False, 1e-6),
+                                                  (2, 1590, 64, 32, True, 1e-5),       # streaming, two sources, ragged last slab and block
+                                                  (24, 4096, 32, 0, True, 1e-5),       # the 128-pixel apply block (B * HW >= 98304)
+                                                  (1, 4096, 512, 0, True, 1e-6)])      # the VAE's width on the streaming path
 def test_groupnorm(B, HW, C0, C1, silu, eps):
     ops = _ops()
     Cc = C0 + C1
@@ -575,7 +578,8 @@ def test_groupnorm(B, HW, C0, C1, silu, eps):
 
 
 @pytest.mark.parametrize("B,HW,C0,C1,silu", [(2, 4096, 320, 0, True), (2, 1024, 640, 320, True), (3, 64, 1280, 1280, True),
-                                             (1, 4096, 320, 320, False), (2, 100, 32, 0, True)])
+                                             (1, 4096, 320, 320, False), (2, 100, 32, 0, True),
+                                             (2, 1590, 64, 32, True)])                  # streaming, carry on both sources, aux with the ragged tail
 def test_groupnorm_reads_the_error_carry_and_writes_the_split_operand(B, HW, C0, C1, silu):
     """icd_groupnorm_carry (UNet option residual = 3, the default): the inputs are tensors of the residual stream, fp16 + one bf8 byte of
     what the rounding lost.  The normalisation reads both (streaming kernels and the one-launch small-map kernel), and the optional
@@ -722,7 +726,12 @@ def test_error_carry_saturates_instead_of_overflowing():
     assert rel_l2(got, ref) <= rel_l2(out, ref) * 1.0001
 
 
-@pytest.mark.parametrize("rows,C", [(1000, 320), (77, 1280), (513, 640), (5, 32)])
+# 320 / 640 / 1280: the multi-row kernels; the others the generic one-wave-per-row kernel: 65 chunks (lane 0 owns two, the others one),
+# 96, 128 and 256 chunks (all four chunk slots of every lane live)
+LAYERNORM_SHAPES = [(1000, 320), (77, 1280), (513, 640), (5, 32), (7, 520), (9, 768), (6, 1024), (5, 2048)]
+
+
+@pytest.mark.parametrize("rows,C", LAYERNORM_SHAPES)
 def test_layernorm(rows, C):
     ops = _ops()
     x = (r16(rows, C, seed=24).float() * 2 + 0.5).half()
@@ -730,6 +739,23 @@ def test_layernorm(rows, C):
     b = 0.1 * torch.randn(C, generator=torch.Generator().manual_seed(26))
     out = ops.layernorm(x.cuda(), g.cuda(), b.cuda())
     assert rel_l2(out, F.layer_norm(x.float(), (C,), g, b, 1e-5)) < TOL
+
+
+@pytest.mark.parametrize("rows,C", LAYERNORM_SHAPES)
+def test_layernorm_stats(rows, C):
+    """(mean, rstd) per row at every width path, and exactly `rows` rows written: the kernels round the row count up to whole waves
+    and row groups, so the two rows behind the output must come back as they were."""
+    ops = _ops()
+    from invertible_cd_amd import _lib
+    x = (r16(rows, C, seed=24).float() * 2 + 0.5).half()
+    mu, var = x.float().mean(1), x.float().var(1, unbiased=False)
+    st = ops.layernorm_stats(x.cuda())
+    assert st.shape == (rows, 2)
+    assert torch.allclose(st[:, 0].cpu(), mu, atol=1e-5, rtol=1e-5) and torch.allclose(st[:, 1].cpu(), (var + 1e-5).rsqrt(), rtol=1e-4)
+    xd = x.cuda()
+    buf = torch.full((rows + 2, 2), -7.0, device="cuda", dtype=torch.float32)
+    _lib.check(_lib.load().icd_layernorm_stats(ops._p(xd), rows, C, 1e-5, ops._p(buf), ops._stream()), "icd_layernorm_stats")
+    assert torch.equal(buf[:rows], st) and torch.all(buf[rows:] == -7.0)
 
 
 @pytest.mark.parametrize("rows,cols,ld,scale", [(37, 77, 80, 1.0), (130, 256, 256, 0.158), (65, 1024, 1024, 0.158),
