@@ -236,6 +236,22 @@ int icd_attention_fused_ex(const void* q, const void* k, const void* vt, void* o
                            int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
                            int64_t vt_batch_stride, float scale, int32_t flags, void* stream);
 
+/* Attention under a per-sample key count (BERT's padding mask; the self-attention of the BLIP text tower behind ImageReward,
+ * utils/metrics.py:283-293).  Layouts and arguments of icd_attention_fused, and key_counts: device int32 [B].  Sample b attends to keys
+ * 0 .. min(key_counts[b], Nk) - 1, every other key has probability exactly zero; a count <= 0 writes zeros for that sample's rows.
+ * One-pass softmax with the key row in registers: Nk <= 128, d a multiple of 8 up to 128, any Nq; anything else returns
+ * ICD_ERR_UNSUPPORTED before a launch. */
+int icd_attention_masked(const void* q, const void* k, const void* vt, void* out, const int32_t* key_counts, int32_t B, int32_t H,
+                         int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
+                         int64_t vt_batch_stride, float scale, void* stream);
+
+/* LayerNorm over the last dim of an fp32 [rows, C] stream (affine, exact two-pass variance about a mean summed in double): the
+ * post-LayerNorm block x <- LN(x + f(x)) with the sum taken from icd_gemm_desc.out_f32, no fp16 rounding between the sum and its
+ * LayerNorm.  out16 (fp16, for the next GEMM) and out32 (fp32, for the next residual add): either may be NULL, not both.
+ * C a multiple of 8 up to 4096, else ICD_ERR_UNSUPPORTED. */
+int icd_layernorm_f32(const float* x, int64_t rows, int32_t C, const float* gamma, const float* beta, float eps, void* out16,
+                      float* out32, void* stream);
+
 /* Materialised attention probabilities in one pass (the layers whose controller reads or edits P, utils/p2p.py:335-338):
  *   probs[(b*H + h), n, 0:Nk] = softmax_key(scale * q[b,n,h,:] . k[b,:,h,:])   fp16, row stride ldp, columns [Nk, ldp) zero.
  * Replaces baddbmm -> softmax of Attention.get_attention_scores without the fp32 score tensor in between; the controller

@@ -159,6 +159,9 @@ SIGNATURES = {
     "icd_unet_kv_cache_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     "icd_attention_fused_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 9
                                + [C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
+    "icd_attention_masked": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 9 + [C.c_int64, C.c_float, C.c_void_p]),
+    "icd_layernorm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "icd_activation": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "icd_embed_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p]),

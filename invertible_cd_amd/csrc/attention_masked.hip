@@ -1,0 +1,186 @@
+// attention_masked.hip - attention under a per-sample key count (BERT's padding mask; the self-attention of the BLIP text tower).
+//
+// Sample b attends to its first min(key_counts[b], Nk) keys; every other key has probability exactly zero.  Nk <= 128, so the whole
+// key row of a query tile lives in registers and the softmax is one pass: no running maximum, no rescaling.
+//
+//   * one wave = 32 query rows of one (sample, head); a block is one wave, nothing is shared, there is no LDS and no barrier.  (The
+//     sequences this serves are 35 tokens: two waves per head.  K and V^T fragments come straight from global memory, 16 B per lane.)
+//   * S^T = K.Q^T on v_mfma_f32_32x32x16_f16, K as the A operand.  K rows enter in a bit-swapped order (MFMA row r <- key r with bits 2
+//     and 3 exchanged), as in attention.hip: the 16 accumulator values of a lane are then two runs of 8 CONSECUTIVE keys, which is the
+//     B-operand layout of O^T += V^T.P^T, so P goes from the accumulators to the second MFMA with no lane movement.
+//   * the mask is a per-element compare of the key index against the wave-uniform count, applied to the scores (-> -inf, so the
+//     probability is exp2(-inf) = 0 exactly; the row maximum is clamped to a finite value so that a count <= 0, where every score is
+//     -inf, gives zeros and not exp2(-inf - -inf) = NaN) and to the V^T fragment (-> 0: pad columns of V^T may hold anything, and
+//     0 * NaN is NaN).  No branch depends on the count.
+//   * the denominator sums the fp16-rounded probabilities the numerator uses; a count <= 0 has denominator 0 and writes zeros.
+#include "common.h"
+
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+struct MaskedK {
+    const half_t* q; const half_t* k; const half_t* vt; half_t* out; const int32_t* counts;
+    int H, Nq, Nk, d, ldq, ldk, ldvt, ldo;
+    long long vt_bs;
+    float scale_log2;
+};
+
+__device__ __forceinline__ float half_max(float v) {                 // max over lanes l and l ^ 32
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float half_sum(float v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// NT = 32-key tiles (Nk <= 32 NT), DT = 32-row tiles of the head dim (d <= 32 DT)
+template <int NT, int DT>
+__global__ __launch_bounds__(64) void attn_masked_kernel(MaskedK p) {
+    const int lane = threadIdx.x, r = lane & 31, hf = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 32;
+    int kc = p.counts[b];
+    kc = kc < p.Nk ? (kc > 0 ? kc : 0) : p.Nk;                        // (0: nothing is attended to)
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    // ---- S^T[key, query] = sum_c K[key, c] Q[query, c]
+    f32x16 s[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[t][i] = 0.f;
+    const int qrow = q0 + r;
+    const half_t* qp = p.q + ((long long)b * p.Nq + (qrow < p.Nq ? qrow : 0)) * p.ldq + h * p.d;
+    const int kswz = (r & 19) | ((r & 4) << 1) | ((r & 8) >> 1);       // bits 2 and 3 exchanged
+    const int ksteps = (p.d + 15) >> 4;
+    for (int ks = 0; ks < ksteps; ++ks) {
+        const int c = ks * 16 + hf * 8;                               // d % 8 == 0: a chunk of 8 is inside the head dim or outside it
+        const bool cin = c < p.d;
+        const f16x8 qf = (cin && qrow < p.Nq) ? *(const f16x8*)(qp + c) : zero8;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int key = t * 32 + kswz;
+            const f16x8 kf = (cin && key < p.Nk) ? *(const f16x8*)(p.k + ((long long)b * p.Nk + key) * p.ldk + h * p.d + c) : zero8;
+            s[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, s[t], 0, 0, 0);
+        }
+    }
+
+    // ---- one-pass softmax over the keys of this lane's query: accumulator i of tile t is key 32 t + 16 (i / 8) + 8 hf + i % 8
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int key = t * 32 + (i >> 3) * 16 + hf * 8 + (i & 7);
+            s[t][i] = key < kc ? s[t][i] * p.scale_log2 : -INFINITY;
+            m = fmaxf(m, s[t][i]);
+        }
+    m = fmaxf(half_max(m), -3.0e38f);                                 // count <= 0: every score is -inf; a finite m keeps -inf - m = -inf
+    f16x8 pf[NT][2];
+    float l = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const half_t ph = (half_t)__builtin_amdgcn_exp2f(s[t][i] - m);      // a masked score is -inf: exactly 0
+            pf[t][i >> 3][i & 7] = ph;
+            l += (float)ph;
+        }
+    l = half_sum(l);
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+
+    // ---- O^T[c, query] = sum_key V^T[c, key] P[query, key]
+    f32x16 o[DT];
+#pragma unroll
+    for (int u = 0; u < DT; ++u)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[u][i] = 0.f;
+    const half_t* vp = p.vt + (long long)b * p.vt_bs + (long long)h * p.d * p.ldvt;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            const int key0 = t * 32 + st * 16 + hf * 8;               // ldvt % 8 == 0 and ldvt >= Nk: a chunk that starts below Nk is inside the row
+#pragma unroll
+            for (int u = 0; u < DT; ++u) {
+                const int c = u * 32 + r;
+                const f16x8 vf = (c < p.d && key0 < p.Nk) ? *(const f16x8*)(vp + (long long)c * p.ldvt + key0) : zero8;
+                u32x4 vw = __builtin_bit_cast(u32x4, vf);              // keys >= count -> 0, as sign-bit masks (no condition registers)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned lo = (unsigned)((key0 + 2 * w - kc) >> 31), hi = (unsigned)((key0 + 2 * w + 1 - kc) >> 31);
+                    vw[w] &= (lo & 0xffffu) | (hi & 0xffff0000u);
+                }
+                o[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vw), pf[t][st], o[u], 0, 0, 0);
+            }
+        }
+
+    // ---- out[query, h d + c]: accumulator i of tile u is head-dim row 32 u + 8 (i / 4) + 4 hf + i % 4
+    if (qrow < p.Nq) {
+        half_t* op = p.out + ((long long)b * p.Nq + qrow) * p.ldo + h * p.d;
+#pragma unroll
+        for (int u = 0; u < DT; ++u)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = u * 32 + g * 8 + hf * 4;
+                if (c < p.d) {
+                    f16x4 v;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = (half_t)(o[u][g * 4 + j] * inv);
+                    *(f16x4*)(op + c) = v;
+                }
+            }
+    }
+}
+
+template <int NT, int DT>
+int launch_masked(const MaskedK& a, int B, hipStream_t st) {
+    hipLaunchKernelGGL((attn_masked_kernel<NT, DT>), dim3((a.Nq + 31) / 32, a.H, B), dim3(64), 0, st, a);
+    ICD_CHECK_LAUNCH("icd_attention_masked");
+    return ICD_OK;
+}
+
+template <int NT>
+int launch_masked_d(const MaskedK& a, int B, hipStream_t st) {
+    if (a.d <= 32) return launch_masked<NT, 1>(a, B, st);
+    if (a.d <= 64) return launch_masked<NT, 2>(a, B, st);
+    if (a.d <= 96) return launch_masked<NT, 3>(a, B, st);
+    return launch_masked<NT, 4>(a, B, st);
+}
+
+}  // namespace
+
+extern "C" int icd_attention_masked(const void* q, const void* k, const void* vt, void* out, const int32_t* key_counts, int32_t B,
+                                    int32_t H, int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
+                                    int64_t vt_batch_stride, float scale, void* stream) {
+    ICD_CHECK_ARG(q && k && vt && out, "icd_attention_masked: null pointer");
+    ICD_CHECK_ARG(key_counts, "icd_attention_masked: key_counts is null");
+    ICD_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "icd_attention_masked: empty shape");
+    ICD_CHECK_ARG(B <= 65535 && H <= 65535, "icd_attention_masked: B and H must be <= 65535");
+    ICD_CHECK_ARG(scale > 0.f, "icd_attention_masked: scale must be positive");
+    if (d <= 0 || d % 8 != 0 || d > 128) {
+        icd_set_error("icd_attention_masked: head dim must be a multiple of 8, <= 128 (got %d)", d);
+        return ICD_ERR_UNSUPPORTED;
+    }
+    if (Nk > 128) {
+        icd_set_error("icd_attention_masked: at most 128 keys (got %d); longer rows go through icd_attention_fused", Nk);
+        return ICD_ERR_UNSUPPORTED;
+    }
+    ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Nk,
+                  "icd_attention_masked: leading dims must be 16-byte aligned and ldvt >= Nk");
+    ICD_CHECK_ARG(ldq >= H * d && ldk >= H * d && ldo >= H * d, "icd_attention_masked: ldq, ldk and ldo must be >= H * d");
+    ICD_CHECK_ARG(vt_batch_stride == 0 || vt_batch_stride >= (int64_t)H * d * ldvt, "icd_attention_masked: vt_batch_stride below H * d * ldvt");
+    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) % 16 == 0 && (uintptr_t)out % 8 == 0 && (uintptr_t)key_counts % 4 == 0,
+                  "icd_attention_masked: q, k and vt must be 16-byte aligned, out 8-byte");
+    MaskedK a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.out = (half_t*)out; a.counts = key_counts;
+    a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
+    a.vt_bs = vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt;
+    a.scale_log2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    if (Nk <= 32) return launch_masked_d<1>(a, B, st);
+    if (Nk <= 64) return launch_masked_d<2>(a, B, st);
+    if (Nk <= 96) return launch_masked_d<3>(a, B, st);
+    return launch_masked_d<4>(a, B, st);
+}

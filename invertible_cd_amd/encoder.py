@@ -86,22 +86,41 @@ def prepare_block(get, names, device, fold_dtype=torch.float64, lam1=None, lam2=
 
 
 # ------------------------------------------------------------------------------------------------------------ the blocks
-def run_blocks(w, prefixes, x, x32, B, T, heads, eps, act, causal, hidden_states=None):
+def run_blocks(w, prefixes, x, x32, B, T, heads, eps, act, causal, hidden_states=None, norm_f32=False, split_qk=False):
     """fp16 stream x [B * T, C] through the blocks whose weights are w[prefix + key] -> (x, its fp32 twin).  x32 is the twin where the
-    front end made one, or None: the first add then reads the fp16 stream.  The stream after each block is appended to `hidden_states`."""
+    front end made one, or None: the first add then reads the fp16 stream.  The stream after each block is appended to `hidden_states`.
+    norm_f32 (needs x32): the LayerNorms read the fp32 twin (icd_layernorm_f32), not its fp16 copy - one rounding fewer in front of
+    every projection.  split_qk (not with causal): q and k leave their GEMM as fp16 + error carry (icd_gemm_desc.out_carry) and the
+    scores are taken from both parts (icd_attention_probs_split, then P.V as a batched GEMM) - the logits lose the rounding of q and k.
+    Both are what the BLIP image tower's peaked attention rows need to stay under 1e-3 over 24 blocks."""
     C = x.shape[1]
     d, ld = C // heads, (T + 7) // 8 * 8
+    if norm_f32 and x32 is None:
+        raise ValueError("run_blocks: norm_f32 needs the fp32 twin of the stream")
+    if split_qk and causal:
+        raise ValueError("run_blocks: split_qk has no causal form")
+
+    def norm(x, x32, k):
+        if norm_f32:
+            return ops.layernorm_f32(x32, w[k + ".w"], w[k + ".b"], eps, want32=False)[0]
+        return ops.layernorm(x, w[k + ".w"], w[k + ".b"], eps)
 
     def add(f, wk, bk, x, x32):
         n32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
         return ops.gemm(f, w[wk], w[bk], resid=x if x32 is None else x32, out32=n32), n32
     for p in prefixes:
-        h = ops.layernorm(x, w[p + "ln1.w"], w[p + "ln1.b"], eps)
-        qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"])
+        h = norm(x, x32, p + "ln1")
         vt = ops.project_vt(h, w[p + "v.w"], B, T, ld)
-        o = ops.attention_fused(qk[:, :C], qk[:, C:], vt, B, heads, T, T, d, d ** -0.5, causal=causal)
+        if split_qk:
+            carry = torch.empty((x.shape[0], 2 * C), device=x.device, dtype=torch.uint8)
+            qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"], out_carry=carry)
+            probs = ops.attention_probs(qk[:, :C], qk[:, C:], B, heads, T, T, d, d ** -0.5, ld=ld, q_carry=carry[:, :C], k_carry=carry[:, C:])
+            o = ops.attention_apply(probs, vt, B, heads, T, d)
+        else:
+            qk = ops.gemm(h, w[p + "qk.w"], w[p + "qk.b"])
+            o = ops.attention_fused(qk[:, :C], qk[:, C:], vt, B, heads, T, T, d, d ** -0.5, causal=causal)
         x, x32 = add(o, p + "o.w", p + "o.b", x, x32)
-        h = ops.layernorm(x, w[p + "ln2.w"], w[p + "ln2.b"], eps)
+        h = norm(x, x32, p + "ln2")
         f = ops.activation(ops.gemm(h, w[p + "fc1.w"], w[p + "fc1.b"]), ACT[act])
         x, x32 = add(f, p + "fc2.w", p + "fc2.b", x, x32)
         if hidden_states is not None:

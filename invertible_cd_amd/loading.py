@@ -207,6 +207,34 @@ def load_inception(path_or_state_dict, device="cuda", config=None):
     return FidInception(config or FID_INCEPTION, sd, device)
 
 
+def load_imagereward(path_or_state_dict, device="cuda", config=None):
+    """The ImageReward model of metrics.calc_ir on the HIP kernels: a state dict, or a `.pt` / `.safetensors` file of one, under this
+    package's names (`vision_model.*` as transformers.BlipVisionModel, `text_encoder.*` as transformers.BlipTextModel,
+    `mlp.layers.{0,2,4,6,7}.*`) or under the ImageReward package's own (`blip.visual_encoder.*`, `blip.text_encoder.*`, `mlp.layers.*`;
+    blip.translate_package_keys - unverified against the real checkpoint, see blip.py).  config: (BlipVisionConfig, BlipTextConfig),
+    default ImageReward-v1.0's.  Nothing is downloaded."""
+    from .blip import ImageReward, IMAGEREWARD_TEXT, IMAGEREWARD_VISION
+    vcfg, tcfg = config or (IMAGEREWARD_VISION, IMAGEREWARD_TEXT)
+    sd = path_or_state_dict
+    if isinstance(sd, (str, os.PathLike)):
+        sd = _read_weights("load_imagereward", os.fspath(sd))
+    return ImageReward(vcfg, tcfg, sd, device)
+
+
+def load_benchmark(path_to_prompts, path_to_images=None):
+    """The reference's load_benchmark (utils/loading.py:151-175) on pandas.  Without `path_to_images`: (captions, file names) of a
+    generation benchmark (columns caption, file_name).  With it: the editing benchmark, a list of
+    (image path, {'before': old_caption, 'after': edited_caption}, blended_words) per row."""
+    import pandas as pd
+    files = pd.read_csv(path_to_prompts)
+    if path_to_images is None:
+        print(f'Generation benchmark: Loading from {path_to_prompts}')
+        return list(files['caption']), list(files['file_name'])
+    print(f'Editing benchmark: Loading prompts, images from {path_to_prompts}, {path_to_images}')
+    return [(f"{path_to_images}/{row['file_name']}", {'before': row['old_caption'], 'after': row['edited_caption']}, row['blended_words'])
+            for _, row in files.reset_index().iterrows()]
+
+
 def load_models(model_id, device, reverse_checkpoint, forward_checkpoint, r=64, w_embed_dim=0, teacher_checkpoint=None,
                 dtype='fp32', components=None, unet_config=None):
     """SD1.5: (ldm_stable, reverse_cons_model, forward_cons_model).  `components` may supply real

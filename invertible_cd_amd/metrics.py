@@ -20,8 +20,15 @@ is preprocessed as one batch); a tensor or array holds one size.  `prompts` are 
 (as everywhere in this package) or strings together with `tokenizer=`.  LPIPS is computed from its definition (a VGG16 feature stack,
 lpips.py) rather than through `piq`, and FID from its own (the FID Inception-v3 of inception.py, `model=` an inception.FidInception, e.g.
 from loading.load_inception; the statistics stream through FidStatistics / icd_moments_f64 on the device, the Frechet distance itself is
-float64 scipy on the host, as in the reference; dims other than 2048 are refused).  ImageReward stays out: its package and weights are
-not available.
+float64 scipy on the host, as in the reference; dims other than 2048 are refused).
+
+    calc_ir(images, prompts, device, batch_size=50, model=..., tokenizer=...)                utils/metrics.py:283-293
+    calc_all(path_to_orig, path_to_edited, path_to_benchmark, outdir, device, clip_model=..., dinov2_model=..., ir_model=...,
+             tokenizer=..., ir_tokenizer=...)                                                utils/metrics.py:327-390
+
+ImageReward is the BLIP pair and reward head of blip.py (`RM.load("ImageReward-v1.0")`: a blip.ImageReward, e.g. from
+loading.load_imagereward); its prompts are (input_ids, attention_mask) of the package's BERT tokenizer.  The architecture is tested against
+`transformers`; the translation of the ImageReward package's checkpoint key names is unverified (blip.py).
 """
 import json
 import math
@@ -103,6 +110,80 @@ def calc_clip_score_images_prompts(images, prompts, device, batch_size=50, model
         et = model.get_text_features(ids[i:i + batch_size])
         scores[i:i + batch_size] = ops.cosine_rows(et, ei).cpu()
     return scores
+
+
+def _ir_tokens(prompts, tokenizer):
+    """(input_ids, attention_mask) [N, T]: a pair of tensors as it is, strings through `tokenizer` called as the ImageReward package
+    calls its BERT tokenizer."""
+    if isinstance(prompts, (tuple, list)) and len(prompts) == 2 and all(isinstance(p, (torch.Tensor, np.ndarray)) for p in prompts):
+        return torch.as_tensor(prompts[0]), torch.as_tensor(prompts[1])
+    if tokenizer is None:
+        raise ValueError("metrics: string prompts need tokenizer= (or pass (input_ids, attention_mask) tensors [N, T])")
+    enc = tokenizer(list(prompts), padding='max_length', truncation=True, max_length=35, return_tensors='pt')
+    return torch.as_tensor(enc["input_ids"]), torch.as_tensor(enc["attention_mask"])
+
+
+@torch.no_grad()
+def calc_ir(images, prompts, device, batch_size=50, model=None, tokenizer=None):
+    """ImageReward of corresponding (image, prompt) pairs -> a list of Python floats, one per pair, in the caller's order (the
+    reference's editing_imagereward).  model=: a blip.ImageReward, e.g. loading.load_imagereward(path).  prompts: (input_ids,
+    attention_mask) tensors [N, T], or strings together with tokenizer= (called with padding='max_length', truncation=True,
+    max_length=35, return_tensors='pt', as the package calls it).  The reference scores the pairs one by one; here they are scored
+    `batch_size` at a time, and only the scores cross to the host."""
+    model = _need_model(model, "a blip.ImageReward, e.g. loading.load_imagereward(path)")
+    ids, mask = _ir_tokens(prompts, tokenizer)
+    n = ids.shape[0]
+    assert _count(images) == n
+    rewards = []
+    for i in range(0, n, batch_size):
+        rewards += model.score(ids[i:i + batch_size], mask[i:i + batch_size], images[i:i + batch_size]).cpu().tolist()
+    return [float(r) for r in rewards]
+
+
+def calc_all(path_to_orig, path_to_edited, path_to_benchmark, outdir, device, clip_model=None, dinov2_model=None, ir_model=None,
+             tokenizer=None, ir_tokenizer=None):
+    """The editing report (utils/metrics.py:327-390): the edited images `path_to_edited`/<number>.<ext>, in numeric order, against the
+    originals and prompts of the editing benchmark (loading.load_benchmark(path_to_benchmark, path_to_orig)), scored in batches of 16
+    and written to `outdir`/editing_metrics_values.json under the reference's keys preservation_clip_score, preservation_dinov2,
+    editing_clip_score and editing_imagereward, the values stringified as there.  Returns that dict.  tokenizer= is CLIP's,
+    ir_tokenizer= ImageReward's BERT tokenizer.  One deliberate difference: an empty `path_to_edited` returns None WITHOUT DELETING
+    THE DIRECTORY (the reference calls shutil.rmtree on it)."""
+    from .generation import load_512, to_pil_images
+    from .loading import load_benchmark
+    _need_model(clip_model, "clip_model=, a clip.CLIPModel, e.g. loading.load_clip(path)")
+    _need_model(dinov2_model, "dinov2_model=, a dinov2.Dinov2Model, e.g. loading.load_dinov2(path)")
+    _need_model(ir_model, "ir_model=, a blip.ImageReward, e.g. loading.load_imagereward(path)")
+    editing_benchmark = load_benchmark(path_to_benchmark, path_to_orig)
+    files = os.listdir(path_to_edited)
+    if len(files) == 0:
+        print(path_to_edited)
+        return None
+    files = [file for file in files if file != 'editing_metrics_values.json']
+    files.sort(key=lambda x: int(x.split('.')[0]))
+    orig_images, edited_prompts, edited_images = [], [], []
+    for j, (image_path, prompts_dict, _) in enumerate(editing_benchmark):
+        if j >= len(files):                          # (the reference's `except IndexError: continue`)
+            continue
+        orig_images.append(to_pil_images(load_512(f'{image_path}')))
+        edited_images.append(to_pil_images(load_512(f'{path_to_edited}/{files[j]}')))
+        edited_prompts.append(prompts_dict['after'])
+    preserve_clip_score = calc_clip_score_images_images(orig_images, edited_images, device, batch_size=16, model=clip_model)
+    preserve_dinov2 = calc_dinov2_images_images(orig_images, edited_images, device, batch_size=16, model=dinov2_model)
+    editing_clip_score = calc_clip_score_images_prompts(edited_images, edited_prompts, device, batch_size=16, model=clip_model,
+                                                        tokenizer=tokenizer)
+    editing_imagereward = calc_ir(edited_images, edited_prompts, device, batch_size=16, model=ir_model, tokenizer=ir_tokenizer)
+    for name, values in (("cs", preserve_clip_score), ("dinov", preserve_dinov2), ("cs edit", editing_clip_score),
+                         ("ir", torch.tensor(editing_imagereward))):
+        print(f'{name} {torch.mean(values)}')
+        print(f'{name} {torch.std(values)}')
+    results = {'preservation_clip_score': str(list(np.array(preserve_clip_score))),
+               'preservation_dinov2': str(list(np.array(preserve_dinov2))),
+               'editing_clip_score': str(list(np.array(editing_clip_score))),
+               'editing_imagereward': str(editing_imagereward)}
+    os.makedirs(outdir, exist_ok=True)
+    with open(f'{outdir}/editing_metrics_values.json', "w") as fp:
+        json.dump(results, fp)
+    return results
 
 
 def _psnr_from_sums(sums, n):

@@ -345,6 +345,33 @@ def attention_fused(q, k, vt, B, H, Nq, Nk, d, scale, causal=False, prescaled=Fa
     return out
 
 
+def attention_masked(q, k, vt, key_counts, B, H, Nq, Nk, d, scale):
+    """attention_fused under a per-sample key count (icd_attention_masked): key_counts int32 [B] on the device, sample b attends to its
+    first min(key_counts[b], Nk) keys and to nothing else; Nk <= 128, d <= 128."""
+    _chk_rows(q, "q"); _chk_rows(k, "k"); _chk16(vt, "vt")
+    assert key_counts.is_cuda and key_counts.dtype == torch.int32 and key_counts.is_contiguous() and tuple(key_counts.shape) == (B,), \
+        "key_counts: need a contiguous cuda int32 [B] tensor"
+    assert q.shape[0] == B * Nq and k.shape[0] == B * Nk and vt.dim() == 3 and vt.shape[0] == B and vt.shape[1] == H * d \
+        and q.shape[1] == H * d and k.shape[1] == H * d, "attention_masked: q [B * Nq, H * d], k [B * Nk, H * d], vt [B, H * d, ld]"
+    out = torch.empty((q.shape[0], q.shape[1]), device=q.device, dtype=torch.float16)
+    _lib.check(_lib.load().icd_attention_masked(_p(q), _p(k), _p(vt), _p(out), _p(key_counts), B, H, Nq, Nk, d, q.stride(0), k.stride(0),
+                                                vt.stride(1), out.stride(0), vt.stride(0), scale, _stream()), "icd_attention_masked")
+    return out
+
+
+def layernorm_f32(x32, gamma, beta, eps, want16=True, want32=True):
+    """LayerNorm of the fp32 rows x32 [rows, C] (icd_layernorm_f32) -> (fp16 copy or None, fp32 copy or None)."""
+    assert x32.is_cuda and x32.dtype == torch.float32 and x32.dim() == 2 and x32.is_contiguous(), "layernorm_f32: need contiguous cuda fp32 rows"
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == x32.shape[1] == beta.numel() \
+        and gamma.is_contiguous() and beta.is_contiguous(), "layernorm_f32: gamma, beta must be contiguous fp32 [C]"
+    assert want16 or want32
+    rows, Cc = x32.shape
+    o16 = torch.empty((rows, Cc), device=x32.device, dtype=torch.float16) if want16 else None
+    o32 = torch.empty((rows, Cc), device=x32.device, dtype=torch.float32) if want32 else None
+    _lib.check(_lib.load().icd_layernorm_f32(_p(x32), rows, Cc, _p(gamma), _p(beta), eps, _p(o16), _p(o32), _stream()), "icd_layernorm_f32")
+    return o16, o32
+
+
 def attention_probs(q, k, B, H, Nq, Nk, d, scale, ld=None, out=None, q_carry=None, k_carry=None, acc=None, edit=None, self_from_base=False,
                     first_cond_sample=0, edit_count=0, group_count=0):
     """P[b*H+h, n, :Nk] = softmax(scale * q.k) as fp16 [B*H, Nq, ld] in one pass (no fp32 score tensor); pad columns zero.
