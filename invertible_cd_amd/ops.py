@@ -424,6 +424,9 @@ def attention_scores(q, k, B, H, Nq, Nk, d, scale, ld):
 
 def attention_apply(p, vt, B, H, Nq, d, out=None):
     """out[b, n, h*d:(h+1)*d] = P[b*H+h, n, :] @ V[b, :, h, :]   with P [B*H, Nq, ld], vt [B, H*d, ld]."""
+    # N is rounded up to 8 columns while heads are d columns apart: a head dim that is no multiple of 8 would write its pad columns
+    # into the next head's range (and past the row for the last head)
+    assert d % 8 == 0, f"attention_apply: head dim {d} is not a multiple of 8"
     ld = p.stride(1)
     if out is None:
         out = torch.empty((B * Nq, H * d), device=p.device, dtype=torch.float16)
