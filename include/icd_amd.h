@@ -633,6 +633,24 @@ int icd_fid_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t 
                    int32_t S, int32_t R, const int32_t* h_first, const int32_t* h_count, const int32_t* h_coef, int32_t h_taps,
                    const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef, int32_t v_taps, void* tmp, void* mid, void* out,
                    void* stream);
+/* Real images into the VAE encoder, on uint8 NHWC images [B, H, W, 3] (device; `images` may start at any byte): what
+ * np.array(PIL.Image.resize((S, S))) (Pillow's default BICUBIC, both axes stretched independently, no crop: utils/generation.py load_512)
+ * followed by image2latent's `torch.from_numpy(arr).float() / 127.5 - 1` and `.to(float16)` give, in one vertical pass with two outputs:
+ *   out   [(b * S + y) * S + x] = 8 fp16 channels, the layout encoder.conv_in reads: channel c < 3 is fp32(u) / 127.5f (a division, not
+ *         a multiplication by a reciprocal), then - 1.0f, then ONE round-to-nearest-even to fp16, uncontracted; channels 3 .. 7 are zero;
+ *   bytes [B, S, S, 3] uint8, the resized image itself (what load_512 returns); NULL skips it and nothing is written there.
+ * Tables as for icd_image_resize_norm (h_* for W -> S, v_* for H -> S, int32 on the device, h_taps / v_taps the row length Pillow uses for
+ * these sizes: tables of other sizes are refused); an axis that keeps its size has [0, 1, 0] taps and reproduces the input bytes.
+ * tmp: uint8 [B * H * S * 3] scratch on the device, 4-byte aligned; out 16-byte aligned; bytes at any address.  Limits: S % 8 == 0
+ * (the encoder halves it three times), S <= 4096, W <= 4096.  64-bit row offsets.  Two launches. */
+int icd_vae_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first, const int32_t* h_count,
+                   const int32_t* h_coef, int32_t h_taps, const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef,
+                   int32_t v_taps, void* tmp, void* out, void* bytes, void* stream);
+/* Decoded images out of the VAE: x NCHW [B, 3, H, W] (fp16, or fp32 when is_f32) -> out uint8 NHWC [B, H, W, 3], the bytes of torch's
+ * `((x / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1) * 255).to(torch.uint8)` in x's own dtype: x * 0.5, + 0.5, clamp to [0, 1], * 255,
+ * each evaluated in fp32 and rounded to x's dtype before the next step, then truncation towards zero.  +-inf clamp to 255 / 0; NaN is
+ * outside the contract.  Any H, W; x aligned to its element, out 4-byte aligned.  One launch. */
+int icd_image_to_u8(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream);
 /* Streaming FID statistics: sum[d] += sum_i x[i][d], outer[a][b] += sum_i x[i][a] x[i][b] over the rows of x fp32 [n, D], in float64.
  * The thread that owns an output element starts from the stored value and adds the rows in index order: two calls give the bits of
  * one call on the concatenation, and sums of several calls (or ranks) simply add.  D % 4 == 0; x 16-byte aligned.  Two launches. */

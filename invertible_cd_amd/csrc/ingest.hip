@@ -4,8 +4,9 @@
 //   icd_clip_preprocess    CLIP / DINOv2: shortest-edge resize, centre crop, normalise, scatter into the ViT's patch matrix
 //   icd_image_resize_norm  LPIPS: both axes stretched to S x S, normalise, NHWC fp16 padded to 8 channels
 //   icd_fid_ingest         FID: resize + crop to uint8 (the bytes ToTensor sees), then bilinear to R x R and 2 u / 255 - 1, fp16 x 8
-// All three share resample_h (the argument checks, the tables' descriptor, the horizontal pass); the vertical passes differ in what they
-// store.  Bandwidth kernels, 64-bit row offsets.
+//   icd_vae_ingest         VAE encoder: both axes stretched to S x S, u / 127.5 - 1, NHWC fp16 padded to 8 channels (+ the resized bytes)
+// All four share resample_h (the argument checks, the tables' descriptor, the horizontal pass); the vertical passes differ in what they
+// store.  icd_image_to_u8 is the way back: a decoded NCHW sample to uint8 NHWC.  Bandwidth kernels, 64-bit row offsets.
 #include "common.h"
 
 namespace {
@@ -138,6 +139,20 @@ struct StoreBytes {                            // the uint8 [B, S, S, 3] interme
         for (int c = 0; c < 3; ++c) mid[it * 3 + c] = (unsigned char)u[c];
     }
 };
+struct StoreVae {                              // the VAE encoder's input: fp16(fp32(u) / 127.5f - 1.0f) as torch evaluates `arr.float() / 127.5 - 1`
+    unsigned char* bytes;                      // and .to(float16): a division, a subtraction, one rounding to fp16; channels 3 .. 7 zero.
+    __device__ void operator()(const PreK& p, long long it, const unsigned (&u)[3]) const {      // bytes (or null): the resized image itself
+#pragma clang fp contract(off)
+        f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float q = (float)u[c] / 127.5f;
+            v[c] = (half_t)(q - 1.0f);
+        }
+        *reinterpret_cast<f16x8*>(p.out + it * 8) = v;
+        if (bytes) StoreBytes{bytes}(p, it, u);
+    }
+};
 
 // Vertical pass, no patches: one thread owns one output pixel, three byte columns of the horizontal pass's rows.
 template <typename Store>
@@ -189,6 +204,42 @@ __global__ __launch_bounds__(256) void fid_bilinear_kernel(const unsigned char* 
         v[c] = (half_t)(2.0f * u - 1.0f);
     }
     *reinterpret_cast<f16x8*>(out + it * 8) = v;
+}
+
+// `(image / 2 + 0.5).clamp(0, 1) * 255` and the cast to uint8 as torch evaluates them on a tensor of type T: every step in fp32, rounded to
+// T before the next one (for T = float the roundings are the fp32 ones).  +-inf clamp; NaN is outside the contract.
+template <typename T>
+__device__ __forceinline__ unsigned sample_to_u8(T x) {
+#pragma clang fp contract(off)
+    T v = (T)((float)x * 0.5f);
+    v = (T)((float)v + 0.5f);
+    v = v < (T)0.f ? (T)0.f : (v > (T)1.f ? (T)1.f : v);
+    v = (T)((float)v * 255.0f);
+    return (unsigned)(int)(float)v;            // [0, 255]: truncation towards zero
+}
+
+// Decoded sample NCHW [B, 3, HW] -> uint8 NHWC [B, HW, 3].  One thread owns four consecutive pixels of the flattened batch (they may
+// straddle two samples when HW % 4 != 0) and stores their 12 bytes as three dwords; the last thread of an odd batch stores bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void image_to_u8_kernel(const T* x, long long npix, long long HW, unsigned char* out) {
+    const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= npix) return;
+    const int n = (int)min(4LL, npix - p0);
+    unsigned char u[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long px = min(p0 + j, npix - 1), b = px / HW;
+        const T* s = x + b * 2 * HW + px;                      // b * 3 HW + (px - b HW)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u[j * 3 + c] = (unsigned char)sample_to_u8(s[c * HW]);
+    }
+    if (n == 4) {
+        unsigned* o = reinterpret_cast<unsigned*>(out + p0 * 3);
+#pragma unroll
+        for (int w = 0; w < 3; ++w) o[w] = u[4 * w] | (u[4 * w + 1] << 8) | (u[4 * w + 2] << 16) | ((unsigned)u[4 * w + 3] << 24);
+    } else {
+        for (int i = 0; i < n * 3; ++i) out[p0 * 3 + i] = u[i];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host side
@@ -310,5 +361,40 @@ extern "C" int icd_fid_ingest(const void* images, int32_t B, int32_t H, int32_t 
     }
     hipLaunchKernelGGL(fid_bilinear_kernel, dim3((unsigned)((opix + 255) / 256)), dim3(256), 0, st, src, (long long)B, S, R, (half_t*)out);
     ICD_CHECK_LAUNCH("icd_fid_ingest (bilinear)");
+    return ICD_OK;
+}
+
+extern "C" int icd_vae_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first, const int32_t* h_count,
+                              const int32_t* h_coef, int32_t h_taps, const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef,
+                              int32_t v_taps, void* tmp, void* out, void* bytes, void* stream) {
+    ICD_CHECK_ARG(images && tmp && out, "icd_vae_ingest: null pointer");
+    ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_vae_ingest: null coefficient table");
+    ICD_CHECK_ARG(B > 0, "icd_vae_ingest: B must be positive (got %d)", B);
+    ICD_CHECK_ARG(H > 0 && W > 0, "icd_vae_ingest: image sizes must be positive (got %d x %d)", H, W);
+    ICD_CHECK_ARG(S > 0 && S % 8 == 0 && S <= 4096, "icd_vae_ingest: S must be a positive multiple of 8, <= 4096 (got %d)", S);
+    hipStream_t st = (hipStream_t)stream;
+    const long long vblocks = ((long long)B * S * S + 255) / 256;
+    const float mean[3] = {0.f, 0.f, 0.f}, stdv[3] = {1.f, 1.f, 1.f};           // unused: StoreVae spells its own arithmetic out
+    PreK p;
+    const int rc = resample_h("icd_vae_ingest", 2.0, images, B, Axis{h_first, h_count, h_coef, h_taps, W, S, 0},
+                              Axis{v_first, v_count, v_coef, v_taps, H, S, 0}, S, 1, 8, mean, stdv, tmp, out, vblocks, st, p);
+    if (rc != ICD_OK) return rc;
+    hipLaunchKernelGGL(resample_v_pixel_kernel<StoreVae>, dim3((unsigned)vblocks), dim3(256), 0, st, p, StoreVae{(unsigned char*)bytes});
+    ICD_CHECK_LAUNCH("icd_vae_ingest (vertical)");
+    return ICD_OK;
+}
+
+extern "C" int icd_image_to_u8(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream) {
+    ICD_CHECK_ARG(x && out, "icd_image_to_u8: null pointer");
+    ICD_CHECK_ARG(B > 0 && H > 0 && W > 0, "icd_image_to_u8: B, H, W must be positive (got %d, %d, %d)", B, H, W);
+    ICD_CHECK_ARG(((uintptr_t)x & (is_f32 ? 3 : 1)) == 0 && ((uintptr_t)out & 3) == 0,
+                  "icd_image_to_u8: x must be aligned to its element, out 4-byte aligned");
+    const long long HW = (long long)H * W, npix = (long long)B * HW;
+    const long long blocks = ((npix + 3) / 4 + 255) / 256;
+    ICD_CHECK_ARG(blocks <= 0x7fffffffLL, "icd_image_to_u8: the batch exceeds the grid limit");
+    hipStream_t st = (hipStream_t)stream;
+    if (is_f32) hipLaunchKernelGGL(image_to_u8_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, npix, HW, (unsigned char*)out);
+    else hipLaunchKernelGGL(image_to_u8_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const half_t*)x, npix, HW, (unsigned char*)out);
+    ICD_CHECK_LAUNCH("icd_image_to_u8");
     return ICD_OK;
 }

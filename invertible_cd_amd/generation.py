@@ -324,7 +324,17 @@ class Generator:
         return image
 
     @torch.no_grad()
-    def image2latent(self, image):
+    def image2latent(self, image, return_bytes=False):
+        """A floating-point 4-d tensor is a latent already.  A uint8 [B, H, W, 3] tensor on the device, or a list of uint8 [H, W, 3]
+        device tensors of any sizes (load_512(..., device=)), is resized to 512 x 512 like load_512 and encoded without leaving the
+        device (vae.encode_images); return_bytes: (latent, the resized uint8 [B, 512, 512, 3]).  numpy / PIL images take the
+        reference's host route."""
+        if _is_device_images(image):
+            enc = self.model.vae.encode_images(image, 512, want_bytes=return_bytes)
+            latent = enc['latent_dist'].mean * 0.18215
+            return (latent, enc['images']) if return_bytes else latent
+        if return_bytes:
+            raise ValueError("image2latent: return_bytes needs uint8 images on the device")
         if type(image) is torch.Tensor and image.dim() == 4:
             return image
         if type(image) is list:
@@ -368,10 +378,17 @@ class Generator:
         return all_latent
 
     @torch.no_grad()
-    def ddim_inversion(self, image, n_steps=None, guidance_scale=1, dynamic_guidance=False, tau1=0.4, tau2=0.6, w_embed_dim=0):
+    def ddim_inversion(self, image, n_steps=None, guidance_scale=1, dynamic_guidance=False, tau1=0.4, tau2=0.6, w_embed_dim=0,
+                       device_images=False):
+        """device_images (uint8 images on the device): image_rec is the pair (the images at 512 x 512, the whole decoded batch), both
+        uint8 NHWC on the device."""
         n_steps = self.n_steps if n_steps is None else n_steps
-        latent = self.image2latent(image)
-        image_rec = self.latent2image(latent)
+        if device_images:
+            latent, image_gt = self.image2latent(image, return_bytes=True)
+            image_rec = (image_gt, self.latent2image(latent, return_type='uint8_device'))
+        else:
+            latent = self.image2latent(image)
+            image_rec = self.latent2image(latent)
         return image_rec, self.ddim_loop(latent, is_forward=True, guidance_scale=guidance_scale, n_steps=n_steps,
                                          dynamic_guidance=dynamic_guidance, tau1=tau1, tau2=tau2, w_embed_dim=w_embed_dim)
 
@@ -420,14 +437,17 @@ class Generator:
         return all_latent
 
     @torch.no_grad()
-    def cons_inversion(self, image, guidance_scale=0.0, w_embed_dim=0, seed=0):
+    def cons_inversion(self, image, guidance_scale=0.0, w_embed_dim=0, seed=0, device_images=False):
         """Forward (data -> noise) consistency inversion from a noised encoding at `start_timestep`.
+
+        device_images (uint8 images on the device): image_rec is the pair (the images at 512 x 512, the whole decoded batch), both
+        uint8 NHWC on the device.
 
         `seed` may be a list with one seed per image (batched editing): image g is noised with
         randn((1, ...), generator=manual_seed(seed[g])) and every row is what an inversion of that image alone with seed[g] gives.
         An int keeps the one batch-wide draw."""
         alpha_schedule, sigma_schedule = self._schedules()
-        latent = self.image2latent(image)
+        latent, image_gt = self.image2latent(image, return_bytes=True) if device_images else (self.image2latent(image), None)
         groups = None
         if isinstance(seed, (list, tuple)):
             if len(seed) != latent.shape[0]:
@@ -438,7 +458,7 @@ class Generator:
         else:
             noise = torch.randn(latent.shape, generator=torch.Generator().manual_seed(seed)).to(latent.device)
         latent = self.noise_scheduler.add_noise(latent, noise, torch.tensor([self.start_timestep]))
-        image_rec = self.latent2image(latent)
+        image_rec = (image_gt, self.latent2image(latent, return_type='uint8_device')) if device_images else self.latent2image(latent)
         prev_groups, self.prompt_groups = self.prompt_groups, groups
         try:
             with _editing(self.forward_cons_model, True):    # forward steps amplify the per-evaluation error: accurate precision level
@@ -455,8 +475,19 @@ class Generator:
 def _to_uint8_device(image):
     """decoded NCHW sample -> uint8 NHWC on its device: clamp, scale and truncate towards zero in the sample's own dtype, the values
     `(image * 255).astype(np.uint8)` takes on the host (the same elementwise arithmetic; the values lie in [0, 255])."""
+    if image.is_cuda and image.dim() == 4 and image.shape[1] == 3 and image.is_contiguous() and image.dtype in (torch.float16, torch.float32):
+        from . import ops
+        return ops.image_to_u8(image)                  # the same bytes in one launch (icd_image_to_u8)
     image = (image / 2 + 0.5).clamp(0, 1)
     return (image.permute(0, 2, 3, 1) * 255).to(torch.uint8).contiguous()
+
+
+def _is_device_images(image):
+    """uint8 NHWC images on the device: a [B, H, W, 3] tensor or a list of [H, W, 3] tensors"""
+    if type(image) is torch.Tensor:
+        return image.dtype == torch.uint8 and image.is_cuda and image.dim() == 4
+    return type(image) is list and len(image) > 0 and all(
+        type(i) is torch.Tensor and i.dtype == torch.uint8 and i.is_cuda and i.dim() == 3 for i in image)
 
 
 def latent2image(vae, latents, on_device=False):
@@ -489,9 +520,13 @@ def init_latent_groups(latent, model, height, width, generator, n_groups, n_prom
     return latent, latents
 
 
-def load_512(image_path, left=0, right=0, top=0, bottom=0):
+def load_512(image_path, left=0, right=0, top=0, bottom=0, device=None):
+    """device=None: the reference's function, the file resized to 512 x 512 on the host.  With a device the file's RGB bytes are
+    uploaded as they are, uint8 [H, W, 3]; Generator.image2latent resizes them there (the same bytes, icd_vae_ingest)."""
     from PIL import Image
     image = np.array(Image.open(image_path).convert('RGB'))[:, :, :3]
+    if device is not None:
+        return torch.from_numpy(np.ascontiguousarray(image)).to(device)
     return np.array(Image.fromarray(image).resize((512, 512)))
 
 

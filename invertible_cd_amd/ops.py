@@ -716,6 +716,31 @@ def image_resize_norm(images, size, mean, std):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ VAE ends: real images in, uint8 images out
+def vae_ingest(images, size, want_bytes=False):
+    """uint8 NHWC images [B, H, W, 3] on the device -> (fp16 [B * size * size, 8], uint8 [B, size, size, 3] or None): Pillow's
+    np.array(PIL.Image.resize((size, size))) (BICUBIC, both axes stretched, no crop), then fp16(fp32(u) / 127.5 - 1) in the layout the
+    VAE encoder's conv_in reads, channels 3 .. 7 zero; with want_bytes the resized bytes leave the same pass (icd_vae_ingest)."""
+    B, H, W = _chk_images(images, "vae_ingest")
+    tmp = torch.empty((B * H, size, 3), device=images.device, dtype=torch.uint8)
+    out = torch.empty((B * size * size, 8), device=images.device, dtype=torch.float16)
+    bytes_out = torch.empty((B, size, size, 3), device=images.device, dtype=torch.uint8) if want_bytes else None
+    _lib.check(_lib.load().icd_vae_ingest(_p(images), B, H, W, size, *_table_args(W, size, H, size, images.device), _p(tmp), _p(out),
+                                          _p(bytes_out), _stream()), "icd_vae_ingest")
+    return out, bytes_out
+
+
+def image_to_u8(image):
+    """decoded sample NCHW [B, 3, H, W] (contiguous cuda fp16 / fp32) -> uint8 NHWC [B, H, W, 3]: the bytes of
+    `((image / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1) * 255).to(torch.uint8)` in the sample's own dtype (icd_image_to_u8)."""
+    assert image.is_cuda and image.dim() == 4 and image.shape[1] == 3 and image.is_contiguous() \
+        and image.dtype in (torch.float16, torch.float32), "image_to_u8: need a contiguous cuda fp16 / fp32 [B, 3, H, W] tensor"
+    B, _, H, W = image.shape
+    out = torch.empty((B, H, W, 3), device=image.device, dtype=torch.uint8)
+    _lib.check(_lib.load().icd_image_to_u8(_p(image), int(image.dtype == torch.float32), B, H, W, _p(out), _stream()), "icd_image_to_u8")
+    return out
+
+
 def relu(x, inplace=False):
     _chk16(x, "x")
     out = x if inplace else torch.empty_like(x)

@@ -510,10 +510,66 @@ class AutoencoderKL:
         dist = LatentDist(mean, logvar)
         return _Out(latent_dist=dist) if return_dict else (dist,)
 
+    @torch.no_grad()
+    def encode_images(self, images_u8, size=None, want_bytes=False, return_dict=True):
+        """Real images straight into the encoder: uint8 NHWC on the device, [B, H, W, 3] or a list of [H, W, 3] / [b, H, W, 3] tensors
+        whose sizes may differ, resized like np.array(PIL.Image.resize((size, size))) (size=None: their own, common, square size) ->
+        latent_dist, the bits `encode` gives the host route's `torch.from_numpy(arr).float() / 127.5 - 1` of the resized arrays.
+        fp16: icd_vae_ingest writes conv_in's input.  fp32 fidelity: the resized bytes go through the host route's own fp32 values (a
+        256-entry table evaluated by that very expression on the host) into _encode_chunk32.  The images are ingested size by size and
+        encoded in the caller's order, max_chunk at a time like `encode`.  want_bytes: the result also carries the resized bytes as
+        ['images'], uint8 [B, size, size, 3]."""
+        groups = [images_u8] if isinstance(images_u8, torch.Tensor) else list(images_u8)
+        groups = [g[None] if g.dim() == 3 else g for g in groups]
+        for g in groups:
+            if g.dtype != torch.uint8 or g.dim() != 4 or g.shape[3] != 3 or not g.is_cuda:
+                raise ValueError(f"AutoencoderKL.encode_images: expected uint8 [B,H,W,3] on the device, got {g.dtype} {tuple(g.shape)}")
+        if not groups:
+            raise ValueError("AutoencoderKL.encode_images: no images")
+        if size is None:
+            sizes = {tuple(g.shape[1:3]) for g in groups}
+            size = groups[0].shape[1]
+            if len(sizes) != 1 or groups[0].shape[2] != size:
+                raise ValueError(f"AutoencoderKL.encode_images: size=None takes square images of one size, got {sorted(sizes)}")
+        if size <= 0 or size % 8:
+            raise ValueError(f"AutoencoderKL.encode_images: size must be a positive multiple of 8, got {size}")
+        f32 = self.dtype == torch.float32
+        by_size = {}
+        for i, g in enumerate(groups):                           # the images of one size ingest as one batch
+            by_size.setdefault(tuple(g.shape[1:3]), []).append(i)
+        x8, u8 = {}, {}
+        for idx in by_size.values():
+            g = groups[idx[0]] if len(idx) == 1 else torch.cat([groups[i] for i in idx])
+            a, b = ops.vae_ingest(g.contiguous(), size, want_bytes=want_bytes or f32)
+            r0 = 0
+            for i in idx:
+                n = groups[i].shape[0]
+                x8[i], u8[i] = a[r0 * size * size:(r0 + n) * size * size], None if b is None else b[r0:r0 + n]
+                r0 += n
+        one = len(groups) == 1
+        x8 = x8[0] if one else torch.cat([x8[i] for i in range(len(groups))])
+        u8 = None if u8[0] is None else (u8[0] if one else torch.cat([u8[i] for i in range(len(groups))]))
+        B, outs = x8.shape[0] // (size * size), []
+        if f32:
+            lut = (torch.arange(256, dtype=torch.uint8).float() / 127.5 - 1).to(self.device)          # the host route's values, exactly
+        for i in range(0, B, self.max_chunk):
+            n = min(self.max_chunk, B - i)
+            if f32:
+                outs.append(self._encode_chunk32(lut[u8[i:i + n].long()].permute(0, 3, 1, 2).contiguous()))
+            else:
+                outs.append(self._encode_packed(x8[i * size * size:(i + n) * size * size], n, size, size))
+        dist = LatentDist(torch.cat([o[0] for o in outs]).to(self.dtype), torch.cat([o[1] for o in outs]).to(self.dtype))
+        if not return_dict:
+            return (dist,)
+        return _Out(latent_dist=dist, images=u8) if want_bytes else _Out(latent_dist=dist)
+
     def _encode_chunk(self, img):
-        w, cfg = self.w, self.cfg
         B, _, H, W = img.shape
-        x = ops.pack_nchw(img)
+        return self._encode_packed(ops.pack_nchw(img), B, H, W)
+
+    def _encode_packed(self, x, B, H, W):
+        """x: the token-major fp16 [B * H * W, 8] input of conv_in (channels past the image's zero)"""
+        w, cfg = self.w, self.cfg
         xc = self._oc(B * H * W, w["encoder.conv_in.weight"].shape[0], x)
         x = ops.conv3x3(x, B, H, W, w["encoder.conv_in.weight"], w["encoder.conv_in.bias"], out_carry=xc)
         nb = len(cfg.block_out_channels)
