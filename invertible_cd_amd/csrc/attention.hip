@@ -10,18 +10,15 @@
 //     independent softmax / MFMA streams to interleave).  KV tiles of 64 keys, double-buffered in LDS via
 //     global_load_lds (K tile [64][dpad16], V^T tile [dpad32][64]; V arrives already transposed from the to_v GEMM
 //     epilogue, so both MFMA operands are K-contiguous and no transposing LDS read is needed).
-//   * S^T = K.Q^T with v_mfma_f32_32x32x16_f16 (K as A operand, Q fragments held in registers as B operand): each lane
-//     owns ONE query column and 32 of the tile's 64 keys, so the online-softmax row reductions are in-lane plus one
-//     cross-half shuffle.  The softmax scale is folded into the exp2 argument (one FMA + one v_exp_f32 per score);
-//     key masking exists only in a peeled instantiation for a ragged last tile.
-//   * O^T += V^T.P^T reuses the S^T accumulator registers directly as the B operand: K rows enter the S^T MFMA in a
-//     bit-swapped order so the k-slots of a lane are 8 consecutive keys and a V^T fragment is one ds_read_b128.
-//     P never leaves registers.
+//   * S^T = K.Q^T and O^T += V^T.P^T in the fragment layout of attn_frag.h (one query column per lane, P from the S^T
+//     accumulators to the second MFMA without leaving registers, a V^T fragment is one ds_read_b128).  The softmax scale
+//     is folded into the exp2 argument (one FMA + one v_exp_f32 per score); key masking exists only in a peeled
+//     instantiation for a ragged last tile.
 //   * when the padded head dim leaves a free V^T row (d = 40, 80, ...) that row is loaded with ones and the MFMA itself
 //     accumulates the softmax denominator (with exactly the fp16-rounded P the numerator uses): no VALU row sums.
 //   * XCD-aware block order: the q-tiles of one (b, h) run on one XCD so its K/V stay in that XCD's L2.
 #include <type_traits>
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
@@ -39,8 +36,6 @@ __device__ __forceinline__ int k_swz(int row, int chunk) {
     return chunk;
 }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct AttnK {
     const half_t* q; const half_t* k; const half_t* vt; half_t* out;
     int B, H, Nq, Nk, d, ldq, ldk, ldvt, ldo;
@@ -54,9 +49,6 @@ struct AttnK {
 //
 // The loop is VALU-issue bound (PMC: VALU pipe 70 % busy with two waves per SIMD, MFMA pipe 25 %), so everything that is
 // not exp / scale / convert / max is kept out of the steady state:
-//   * K rows are fed to the S^T MFMA in a bit-swapped order (row r <- key r with bits 2 and 3 exchanged), so that the 8
-//     accumulator values a lane contributes to one P^T k-slot are 8 CONSECUTIVE keys: every V^T fragment is one
-//     ds_read_b128 and P goes from the accumulators to the B operand with no register shuffles;
 //   * the global -> LDS source pointers are computed once and bumped per tile; the ragged last tile (key masking,
 //     guarded loads) is peeled out of the loop, and the loop is unrolled by two so LDS offsets are immediates;
 //   * row sums come from the MFMA pipe (a ones-row of V^T when the padded head dim leaves one, otherwise one extra MFMA
@@ -125,12 +117,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
     const int tid = threadIdx.x, l = tid & 63, lr = l & 31, lh = l >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x;
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    const int bid = xcd_block(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt, bh = bid / p.nqt;
     const int b = bh / p.H, h = bh - b * p.H;
     const int q0 = qt * (128 * QT) + wv * (32 * QT);
@@ -139,12 +126,12 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
     const half_t* Kb = p.k + (long long)b * p.Nk * p.ldk + h * p.d;
     const half_t* Vb = p.vt + (long long)b * p.vt_bs + (long long)h * p.d * p.ldvt;
 
-    // Q fragments: lane = query row q0 + 32u + lr, head-dim offset ks*16 + lh*8
     f16x8 qf[QT][KS];
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
         const int qrow = q0 + u * 32 + lr;
         const half_t* qp = p.q + ((long long)b * p.Nq + qrow) * p.ldq + h * p.d;
+        // (written out: a shared Q-fragment loader changed the schedule of the kernels using it, profiles/r17_attn_isa.txt)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int dd = ks * 16 + lh * 8;
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
     // ---- LDS read offsets (bytes, buffer 0; buffer / sub-tile offsets are immediates) ------------------------------
     int kbase[KS], vbase[4];
     {
-        const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);      // bits 2 and 3 exchanged
+        const int prow = attn_key_row(lr);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) kbase[ks] = (prow * NCH + k_swz<NCH>(prow, ks * 2 + lh)) * 16;
         const int x = (lr >> 1) & 7;
@@ -320,12 +307,12 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
 #pragma unroll
             for (int u = 0; u < QT; ++u) {
                 const int last = CAUSAL ? min(p.Nk - 1, q0 + u * 32 + lr) : p.Nk - 1;    // last key this query may see
-                const int lim = last - t * 64 - 8 * lh;  // (constant) > (one per-lane limit): no scalar register per key slot
+                const int lim = last - t * 64 - 8 * lh;  // attn_key > last as (constant slot) > (one per-lane limit): no scalar register per key slot
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
-                        if (kt * 32 + 16 * (e >> 3) + (e & 7) > lim) s[u][kt][e] = -INFINITY;
+                        if (attn_key_slot(kt, e) > lim) s[u][kt][e] = -INFINITY;
             }
         }
     };
@@ -347,7 +334,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
                     vf16[kt][r] = *reinterpret_cast<const f16x8*>(smem + vbase[kt] + (BO + r * 2048));
         }
         __builtin_amdgcn_sched_barrier(0);
-        // ---- softmax numerators (lane owns query column lr; element e of s[kt] is key 32kt + 16(e>>3) + 8lh + (e&7)) ----
+        // ---- softmax numerators (lane owns query column lr) ----
         f16x8 pf[QT][4];
 #pragma unroll
         for (int u = 0; u < QT; ++u) {
@@ -357,11 +344,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
                 mx0 = fmaxf(fmaxf(mx0, s[u][0][e]), s[u][1][e]);
                 mx1 = fmaxf(fmaxf(mx1, s[u][0][e + 1]), s[u][1][e + 1]);
             }
-            float mx = fmaxf(mx0, mx1);
-            {   // other half-wave's maximum with v_permlane32_swap (VALU; a ds_bpermute would drain the LDS queue)
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            }
+            const float mx = half_max(fmaxf(mx0, mx1));
             if (MODE != 0) {
                 // s already is (base-2 exponent - M).  The first tile fixes M at its row maximum; afterwards M moves only when a
                 // maximum outgrows it by more than 2^8 (lazy rescale, as MODE 0).  At a move by delta: O and l shrink by 2^-delta, the
@@ -539,20 +522,18 @@ __global__ __launch_bounds__(256, OCC) void attn_fused_kernel(AttnK p) {
                 }
             }
     } else {
-    // ---- normalise and store: lane holds 4 consecutive head-dim columns of query row q0 + 32u + lr ----
+    // ---- normalise and store query row q0 + 32u + lr ----
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
         float l_tot;
         if (ONES) l_tot = __shfl(o[u][ODT - 1][15], lr + 32);   // row DT*32-1 of O^T = sum_k P (the V^T ones-row), upper half-wave
         else if (LS_MFMA) l_tot = l_run[u];
-        else {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run[u]), __float_as_uint(l_run[u]), false, false);
-            l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-        }
+        else l_tot = half_sum(l_run[u]);
         const float inv = 1.0f / l_tot;
         const int qrow = q0 + u * 32 + lr;
         if (qrow < p.Nq) {
             half_t* op = p.out + ((long long)b * p.Nq + qrow) * p.ldo + h * p.d;
+            // (attn_store_direct written out: through the call all 21 instantiations schedule differently, profiles/r17_attn_isa.txt)
 #pragma unroll
             for (int i = 0; i < ODT; ++i)
 #pragma unroll
@@ -586,12 +567,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
     const int tid = threadIdx.x, l = tid & 63, lr = l & 31, lh = l >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nchunk = (p.Nq + 32 * tiles_per_wave * 4 - 1) / (32 * tiles_per_wave * 4);      // blocks per (b, h)
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x;
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    const int bid = xcd_block(blockIdx.x, gridDim.x);
     const int qc = bid % nchunk, bh = bid / nchunk;
     const int b = bh / p.H, h = bh - b * p.H;
     const half_t* Kb = p.k + (long long)b * p.Nk * p.ldk + h * p.d;
@@ -600,8 +576,8 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
 #pragma unroll
     for (int e = 0; e < 8; ++e) z8[e] = (half_t)0.f;
 
-    // K fragments (A operand of S^T = K.Q^T): lane row = key 32kt + perm(lr) (bits 2,3 exchanged, see attn_fused_kernel)
-    const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);
+    // K fragments (A operand of S^T = K.Q^T): lane row = key 32kt + attn_key_row(lr)
+    const int prow = attn_key_row(lr);
     f16x8 kf[KT][KS];
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
@@ -627,7 +603,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
         const int qrow = q0 + lr;
         const half_t* qp = p.q + ((long long)b * p.Nq + qrow) * p.ldq + h * p.d;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {                 // (written out, as in attn_fused_kernel)
             const int dd = ks * 16 + lh * 8;
             qf[ks] = (qrow < p.Nq && dd < p.d) ? *reinterpret_cast<const f16x8*>(qp + dd) : z8;
         }
@@ -638,7 +614,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
     float mb[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        mb[e] = (KT - 1) * 32 + 16 * (e >> 3) + 8 * lh + (e & 7) >= p.Nk ? -INFINITY : 0.f;
+        mb[e] = attn_key(KT - 1, e, lh) >= p.Nk ? -INFINITY : 0.f;
         asm volatile("" : "+v"(mb[e]));                   // opaque: or the select is rematerialised inside the loop, predicates and all
     }
     // Q fragments of TWO tiles ahead are in flight under a tile's work (three named register sets, no copies): with one tile ahead the
@@ -654,8 +630,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
                 s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kt][ks], qf[ks], ks == 0 ? zero16 : s[kt], 0, 0, 0);
-        // element e of s[kt] is key 32kt + 16(e>>3) + 8lh + (e&7); the slots past Nk (all in the last tile: 64 < Nk <= 96) get -inf
-        // from the per-lane bias `mb`, exact softmax over the rest
+        // the key slots past Nk (all in the last tile: 64 < Nk <= 96) get -inf from the per-lane bias `mb`, exact softmax over the rest
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[KT - 1][e] += mb[e];
         float mx = -INFINITY;
@@ -664,10 +639,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
 #pragma unroll
             for (int e = 0; e < 16; ++e)
                 if (kt * 2 + (e >> 3) < STL) mx = fmaxf(mx, s[kt][e]);
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
+        mx = half_max(mx);
         const float nmc = -mx * c;
         float rs = 0.f;
         f16x8 pf[ST];
@@ -686,27 +658,9 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
 #pragma unroll
             for (int i = 0; i < DT; ++i)
                 o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[st][i], pf[st], st == 0 ? zero16 : o[i], 0, 0, 0);
-        float l_tot;
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-            l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-        }
-        const float inv = 1.0f / l_tot;
+        const float inv = 1.0f / half_sum(rs);
         const int qrow = q0 + lr;
-        if (qrow < p.Nq) {
-            half_t* op = p.out + ((long long)b * p.Nq + qrow) * p.ldo + h * p.d;
-#pragma unroll
-            for (int i = 0; i < DT; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int dc = i * 32 + 8 * g + 4 * lh;
-                    if (dc < p.d) {
-                        f16x4 v = {(half_t)(o[i][4 * g] * inv), (half_t)(o[i][4 * g + 1] * inv),
-                                   (half_t)(o[i][4 * g + 2] * inv), (half_t)(o[i][4 * g + 3] * inv)};
-                        *reinterpret_cast<f16x4*>(op + dc) = v;
-                    }
-                }
-        }
+        if (qrow < p.Nq) attn_store_direct(p.out + ((long long)b * p.Nq + qrow) * p.ldo + h * p.d, o, inv, p.d, lh);
     };
     auto live = [&](int t) { return t < tiles_per_wave && q_first + t * 32 < p.Nq; };
     for (int t = 0; live(t); t += 3) {
@@ -722,8 +676,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnK p, int tiles_p
 // utils/p2p.py:335-338): P[b*H + h][q][key] = softmax_key(scale * q . k) as fp16, straight from the S^T accumulators -
 // the fp32 score tensor of the old path (QK^T GEMM -> 4 B/element out, 4 B/element back in, softmax kernel) never exists.
 // A wave owns one 32-query tile of one (batch, head): Q fragments in registers, K fragments streamed from global / L2
-// (one k-tile ahead) as the MFMA A operand in the bit-swapped row order that makes a lane's 16 accumulators two runs of 8
-// consecutive keys.  <= 96 keys (cross-attention): the three S^T tiles stay in registers, exact softmax.  More keys
+// (one k-tile ahead) as the MFMA A operand, fragment layout of attn_frag.h.  <= 96 keys (cross-attention): the three S^T tiles stay in registers, exact softmax.  More keys
 // (self-attention of the <= 32^2 layers): two sweeps over K - running (max, sum) first, then S^T again and
 // P = exp2(s - max) / sum; recomputing 4*Nq*Nk*d flops is far cheaper than 8 B/element of HBM traffic.  Probabilities
 // leave through a per-wave LDS patch as 128-B row segments; pad columns [Nk, ldp) are written as zeros.
@@ -737,7 +690,6 @@ struct ProbsK {
 
 // 8 carry bytes -> 8 fp16 values bf8_e5m2(byte) (UNSCALED: a bf8 e5m2 number is the top byte of the fp16 with the same value)
 __device__ __forceinline__ f16x8 carry8_as_f16(const u32x2 w) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 r = {__builtin_amdgcn_perm(w[0], 0u, 0x050c040cu), __builtin_amdgcn_perm(w[0], 0u, 0x070c060cu),
                      __builtin_amdgcn_perm(w[1], 0u, 0x050c040cu), __builtin_amdgcn_perm(w[1], 0u, 0x070c060cu)};
     return __builtin_bit_cast(f16x8, r);
@@ -805,7 +757,7 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
     };
     QFrags qf;
     if constexpr (!FEW) load_q(qf, bq);                  // (the few-keys path loads it after the base prompt's probabilities: registers)
-    const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);
+    const int prow = attn_key_row(lr);
     auto load_k_of = [&](f16x8 (&kf)[KF], int kt, int bs) {
         const long long koff0 = (long long)bs * a.Nk * a.ldk + h * a.d;
         const int key = kt * 32 + prow;
@@ -836,18 +788,10 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            s[e] = 16 * (e >> 3) + (e & 7) < a.Nk - kt * 32 - 8 * lh ? s[e] * c : -INFINITY;      // key < Nk
+            s[e] = attn_key_slot(0, e) < a.Nk - kt * 32 - 8 * lh ? s[e] * c : -INFINITY;      // attn_key(kt, e, lh) < Nk
         }
     };
     auto scores = [&](f32x16& s, const f16x8 (&kf)[KF], int kt) { scores_of(s, kf, qf, kt); };
-    auto half_swap_max = [&](float v) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-    };
-    auto half_swap_sum = [&](float v) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        return __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    };
     half_t* Pb = a.p + ((long long)bh * a.Nq + q0) * a.ldp;
     half_t* Ab = EPI && ep.acc && b >= ep.b0 ? ep.acc + ((long long)(r0 * a.H + h) * a.Nq + q0) * a.ldp : nullptr;
     // one k-tile of probabilities (this lane: query lr, keys 32kt + 16j + 8lh .. +7, j = 0, 1) -> patch -> global rows
@@ -904,14 +848,14 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
                     for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[kt][e]);
                 }
             }
-            mx = half_swap_max(mx);
+            mx = half_max(mx);
             float rs = 0.f;
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt)
                 if (kt < nt)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) { s[kt][e] = __builtin_amdgcn_exp2f(s[kt][e] - mx); rs += s[kt][e]; }
-            const float inv = 1.0f / half_swap_sum(rs);
+            const float inv = 1.0f / half_sum(rs);
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt)
                 if (kt < nt)
@@ -1055,9 +999,9 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
         __syncthreads();
     }
     {   // merge the two half-waves (each saw 16 of every 32 keys); a half that saw only masked keys has m = -inf, l = 0
-        const float m_all = half_swap_max(m_run);
+        const float m_all = half_max(m_run);
         const float mine = m_run == -INFINITY ? 0.f : l_run * __builtin_amdgcn_exp2f(m_run - m_all);
-        l_run = half_swap_sum(mine);
+        l_run = half_sum(mine);
         m_run = m_all;
     }
     const float inv = 1.0f / l_run;
@@ -1137,7 +1081,7 @@ static int attention_probs_run(const void* q, const void* qc, const void* k, con
     ProbsK a;
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.p = (half_t*)probs;
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldp = ldp;
-    a.scale_log2 = scale * 1.4426950408889634f;
+    a.scale_log2 = scale * ATTN_LOG2E;
     a.qc = (const unsigned char*)qc; a.kc = (const unsigned char*)kc;
     ProbsEpi ep{nullptr, nullptr, nullptr, 0, 0, 1};
     if (epi) {
@@ -1214,7 +1158,7 @@ extern "C" int icd_attention_fused_ex(const void* q, const void* k, const void* 
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
     a.vt_bs = vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt;
     const bool presc = (flags & ICD_ATTN_Q_PRESCALED) != 0;
-    a.scale_log2 = presc ? 1.0f : scale * 1.4426950408889634f;
+    a.scale_log2 = presc ? 1.0f : scale * ATTN_LOG2E;
     // MODE 1 / 2 kernels (exponent offset subtracted by the MFMA); a causal mask has the fast form at head dim 64 only
     const bool fast = presc && !(flags & ICD_ATTN_TUNE_MODE0) && (!(flags & ICD_ATTN_CAUSAL) || d == 64);
     a.nqt = 0;

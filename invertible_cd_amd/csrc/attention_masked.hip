@@ -5,19 +5,16 @@
 //
 //   * one wave = 32 query rows of one (sample, head); a block is one wave, nothing is shared, there is no LDS and no barrier.  (The
 //     sequences this serves are 35 tokens: two waves per head.  K and V^T fragments come straight from global memory, 16 B per lane.)
-//   * S^T = K.Q^T on v_mfma_f32_32x32x16_f16, K as the A operand.  K rows enter in a bit-swapped order (MFMA row r <- key r with bits 2
-//     and 3 exchanged), as in attention.hip: the 16 accumulator values of a lane are then two runs of 8 CONSECUTIVE keys, which is the
-//     B-operand layout of O^T += V^T.P^T, so P goes from the accumulators to the second MFMA with no lane movement.
+//   * S^T = K.Q^T and O^T += V^T.P^T in the fragment layout of attn_frag.h: P goes from the accumulators to the second MFMA with no
+//     lane movement.
 //   * the mask is a per-element compare of the key index against the wave-uniform count, applied to the scores (-> -inf, so the
 //     probability is exp2(-inf) = 0 exactly; the row maximum is clamped to a finite value so that a count <= 0, where every score is
 //     -inf, gives zeros and not exp2(-inf - -inf) = NaN) and to the V^T fragment (-> 0: pad columns of V^T may hold anything, and
 //     0 * NaN is NaN).  No branch depends on the count.
 //   * the denominator sums the fp16-rounded probabilities the numerator uses; a count <= 0 has denominator 0 and writes zeros.
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct MaskedK {
     const half_t* q; const half_t* k; const half_t* vt; half_t* out; const int32_t* counts;
@@ -25,15 +22,6 @@ struct MaskedK {
     long long vt_bs;
     float scale_log2;
 };
-
-__device__ __forceinline__ float half_max(float v) {                 // max over lanes l and l ^ 32
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 // NT = 32-key tiles (Nk <= 32 NT), DT = 32-row tiles of the head dim (d <= 32 DT)
 template <int NT, int DT>
@@ -52,11 +40,12 @@ __global__ __launch_bounds__(64) void attn_masked_kernel(MaskedK p) {
         for (int i = 0; i < 16; ++i) s[t][i] = 0.f;
     const int qrow = q0 + r;
     const half_t* qp = p.q + ((long long)b * p.Nq + (qrow < p.Nq ? qrow : 0)) * p.ldq + h * p.d;
-    const int kswz = (r & 19) | ((r & 4) << 1) | ((r & 8) >> 1);       // bits 2 and 3 exchanged
+    const int kswz = attn_key_row(r);
     const int ksteps = (p.d + 15) >> 4;
     for (int ks = 0; ks < ksteps; ++ks) {
         const int c = ks * 16 + hf * 8;                               // d % 8 == 0: a chunk of 8 is inside the head dim or outside it
         const bool cin = c < p.d;
+        // (written out: a shared Q-fragment loader changed the schedule of every instantiation, profiles/r17_attn_isa.txt)
         const f16x8 qf = (cin && qrow < p.Nq) ? *(const f16x8*)(qp + c) : zero8;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -66,12 +55,13 @@ __global__ __launch_bounds__(64) void attn_masked_kernel(MaskedK p) {
         }
     }
 
-    // ---- one-pass softmax over the keys of this lane's query: accumulator i of tile t is key 32 t + 16 (i / 8) + 8 hf + i % 8
+    // ---- one-pass softmax over the keys of this lane's query
     float m = -INFINITY;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
+            // (attn_key(t, i, hf) written out: as a call the NT = 1 kernels take 4 more SGPRs, profiles/r17_attn_isa.txt)
             const int key = t * 32 + (i >> 3) * 16 + hf * 8 + (i & 7);
             s[t][i] = key < kc ? s[t][i] * p.scale_log2 : -INFINITY;
             m = fmaxf(m, s[t][i]);
@@ -116,21 +106,10 @@ __global__ __launch_bounds__(64) void attn_masked_kernel(MaskedK p) {
             }
         }
 
-    // ---- out[query, h d + c]: accumulator i of tile u is head-dim row 32 u + 8 (i / 4) + 4 hf + i % 4
+    // ---- out[query, h d + c]
     if (qrow < p.Nq) {
         half_t* op = p.out + ((long long)b * p.Nq + qrow) * p.ldo + h * p.d;
-#pragma unroll
-        for (int u = 0; u < DT; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c = u * 32 + g * 8 + hf * 4;
-                if (c < p.d) {
-                    f16x4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = (half_t)(o[u][g * 4 + j] * inv);
-                    *(f16x4*)(op + c) = v;
-                }
-            }
+        attn_store_direct(op, o, inv, p.d, hf);
     }
 }
 
@@ -177,7 +156,7 @@ extern "C" int icd_attention_masked(const void* q, const void* k, const void* vt
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.out = (half_t*)out; a.counts = key_counts;
     a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
     a.vt_bs = vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt;
-    a.scale_log2 = scale * 1.4426950408889634f;
+    a.scale_log2 = scale * ATTN_LOG2E;
     hipStream_t st = (hipStream_t)stream;
     if (Nk <= 32) return launch_masked_d<1>(a, B, st);
     if (Nk <= 64) return launch_masked_d<2>(a, B, st);

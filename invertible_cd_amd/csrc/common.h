@@ -14,6 +14,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // error plumbing (host)
 void icd_set_error(const char* fmt, ...);
@@ -60,6 +61,14 @@ static __device__ __attribute__((aligned(256))) unsigned char icd_zero_page[256]
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// Block b runs on XCD b % 8 (observed, speed only).  xcd_block renumbers the nblk blocks of a launch so that every XCD gets one
+// contiguous range of the sequence: neighbours in it (the q-tiles of one (batch, head), the n-tiles of one activation tile) share that
+// XCD's L2.  A permutation of [0, nblk) for any nblk.
+__device__ __forceinline__ int xcd_block(int bid, int nblk) {
+    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }

@@ -28,6 +28,7 @@
 #include <string.h>
 #include <type_traits>
 #include "gemm_common.h"
+#include "attn_frag.h"
 
 using namespace icd_gemm_detail;
 
@@ -47,8 +48,7 @@ constexpr int BN = 128;
 //     16ks + 8(e >> 2) + 4lh + (e & 3), e = 0..7, of k-step ks in registers 8(ks & 1) + e of acc[i][ks >> 1]; the sum over the
 //     head dim does not care about the order, so the K fragments are simply loaded in the same permuted order (two 8-B
 //     loads per fragment instead of one 16-B load);
-//   * K rows enter bit-swapped (bits 2 and 3 of the key index) so the 8 probabilities a lane feeds to one P^T k-slot are
-//     8 consecutive keys and every V^T fragment is one 16-B load (same trick as attention.hip);
+//   * K rows, P and V^T fragments in the layout of attn_frag.h;
 //   * fused LayerNorm correction, bias, the softmax scale and log2(e) are applied to the accumulators in fp32 before the
 //     single fp16 rounding of q;
 //   * O goes through a private 4.5 KiB LDS patch per wave and leaves as 128-B row segments.
@@ -66,7 +66,7 @@ __device__ __forceinline__ void xattn_epilogue(const GemmK& p, f32x16 (&acc)[2][
     f16x8 z8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) z8[e] = (half_t)0.f;
-    const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);
+    const int prow = attn_key_row(lr);
     f16x8 kf[KT][KS];
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
@@ -112,7 +112,7 @@ __device__ __forceinline__ void xattn_epilogue(const GemmK& p, f32x16 (&acc)[2][
                     qf[2 * j + (g >> 1)][4 * (g & 1) + e] = (half_t)(v * p.x_scale_log2);
                 }
             }
-        // ---- S^T[key][q] over 96 key slots, exact softmax (element e of s[kt] is key 32kt + 16(e>>3) + 8lh + (e&7)) ----
+        // ---- S^T[key][q] over 96 key slots, exact softmax ----
         f32x16 s[KT];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
@@ -126,13 +126,10 @@ __device__ __forceinline__ void xattn_epilogue(const GemmK& p, f32x16 (&acc)[2][
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                if (kt * 32 + 16 * (e >> 3) + (e & 7) >= kl) s[kt][e] = -INFINITY;      // key >= x_nk
+                if (attn_key_slot(kt, e) >= kl) s[kt][e] = -INFINITY;      // attn_key >= x_nk
                 mx = fmaxf(mx, s[kt][e]);
             }
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
+        mx = half_max(mx);
         float rs = 0.f;
         f16x8 pf[ST];
 #pragma unroll
@@ -149,13 +146,9 @@ __device__ __forceinline__ void xattn_epilogue(const GemmK& p, f32x16 (&acc)[2][
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[st][dt], pf[st], st == 0 ? zero16 : o[dt], 0, 0, 0);
-        float l_tot;
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-            l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-        }
-        const float inv = 1.0f / l_tot;
-        // ---- O tile [32 queries][64 dims] through the wave's LDS patch (row stride 72 halves), out as 128-B rows ----
+        const float inv = 1.0f / half_sum(rs);
+        // ---- O tile [32 queries][64 dims] through the wave's LDS patch, out as 128-B rows (written out here and in gemm_big.hip: as
+        //      shared patch functions both hosts' epilogues schedule differently, profiles/r17_attn_isa.txt) ----
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -803,7 +796,7 @@ static int gemm_run(const icd_gemm_desc* d, void* stream, icd_gemm_plan_info* in
     const int batch = d->batch > 0 ? d->batch : 1;
     k.xk = (const half_t*)d->xattn_k; k.xvt = (const half_t*)d->xattn_vt;
     k.x_nk = d->xattn_nk; k.x_ldk = d->xattn_ldk; k.x_ldvt = d->xattn_ldvt; k.x_vt_bs = d->xattn_vt_bs;
-    k.x_scale_log2 = d->xattn_scale * 1.4426950408889634f;
+    k.x_scale_log2 = d->xattn_scale * ATTN_LOG2E;
     if (d->xattn_k) {
         // query projection + cross-attention in one launch: out = softmax(scale (A W^T + ...) K^T) V per 64-wide head
         ICD_CHECK_ARG(d->xattn_vt && d->xattn_scale > 0.f, "icd_gemm(xattn): xattn_vt and a positive xattn_scale are required");

@@ -13,6 +13,7 @@
 //     gather is gemm_conv_gather.h (the ping-pong tiles, gemm_pp.hip and gemm_pp320.hip, keep copies of their own).
 #include <type_traits>
 #include "gemm_common.h"
+#include "attn_frag.h"
 #include "gemm_conv_gather.h"
 #include "gemm_epilogue.h"
 
@@ -29,7 +30,9 @@ namespace {
 // 96 keys (stride 208 B).  The four query tiles are first rounded to fp16 q (128 accumulator registers -> 64), then processed in
 // pairs on one register-resident set of K fragments and one of V^T fragments (reading each fragment from LDS right before
 // its MFMA left ~36 exposed LDS latencies per tile: 17 us of epilogue per block).  O leaves through a private LDS patch per
-// wave as 128-B row segments.
+// wave as 128-B row segments.  Fragment layout: attn_frag.h.  The row swap, the half-wave reductions and the patch epilogue are written out
+// here: with attn_key_row / half_max / half_sum alone two of the four hosts take another schedule, with the patch functions all four
+// (profiles/r17_attn_isa.txt).
 constexpr int XA_K_OFF = 0, XA_K_LD = 520, XA_V_OFF = 96 * XA_K_LD, XA_V_LD = 208, XA_TABLE_OFF = XA_V_OFF + 256 * XA_V_LD;
 constexpr int XA_PATCH_OFF = XA_TABLE_OFF + 5 * 256 * 8, XA_SMEM = XA_PATCH_OFF + 8 * 32 * 72 * 2;     // 49920 + 53248 + 10240 + 36864
 static_assert(XA_SMEM <= 160 * 1024, "fused cross-attention: LDS budget");
@@ -69,7 +72,7 @@ __device__ __forceinline__ void xattn_epilogue_big(const GemmK& p, f32x16 (&acc)
     __syncthreads();
     const unsigned char* Kl = smem + XA_K_OFF + wn * 128;  // this wave's head: 64 dims = 128 B into every key row
     const unsigned char* Vl = smem + XA_V_OFF + wn * 64 * XA_V_LD;
-    const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);
+    const int prow = (lr & 0x13) | ((lr & 4) << 1) | ((lr & 8) >> 1);      // attn_key_row(lr), written out (see above)
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     half_t* patch = reinterpret_cast<half_t*>(smem + XA_PATCH_OFF) + wv * (32 * 72);
     const int ncol = n0 + wn * 64;

@@ -44,14 +44,12 @@ __device__ __forceinline__ long long out_row(const GemmK& p, int m) {
     return (long long)(f * (unsigned)m + s * __umulhi((unsigned)m, p.orm_magic) + c);
 }
 
-// block id -> (m-tile, n-tile).  Block b runs on XCD b % 8 (observed, speed only): every XCD gets a contiguous range of
-// the tile sequence, and inside it tiles are ordered in groups of `gm` m-tiles with the n-tile index outermost, so the
-// ~32 blocks an XCD runs concurrently cover gm x (32 / gm) tiles: they share gm activation tiles and 32 / gm weight tiles
-// through that XCD's L2 (12 operand tiles instead of 33 for gm = 8), and most global -> LDS loads become L2 hits.
+// block id -> (m-tile, n-tile).  Every XCD gets a contiguous range of the tile sequence (xcd_block, common.h), and inside
+// it tiles are ordered in groups of `gm` m-tiles with the n-tile index outermost, so the ~32 blocks an XCD runs concurrently
+// cover gm x (32 / gm) tiles: they share gm activation tiles and 32 / gm weight tiles through that XCD's L2 (12 operand tiles
+// instead of 33 for gm = 8), and most global -> LDS loads become L2 hits.
 __device__ __forceinline__ void tile_of_block(int bid, int nbm, int nbn, int gm, int& mt, int& nt) {
-    const int nblk = nbm * nbn;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    bid = xcd_block(bid, nbm * nbn);
     const int per_group = gm * nbn;
     const int g = bid / per_group, rem = bid - g * per_group;
     const int rows = min(gm, nbm - g * gm);

@@ -822,6 +822,28 @@ def _attn_ref_exp2(qp, k, v, B, H, Nq, Nk, d, causal=False):
     return (torch.softmax(e, -1) @ vh).permute(0, 2, 1, 3).reshape(B * Nq, H * d)
 
 
+@pytest.mark.parametrize("B,H,Nq,Nk,d", [(2, 8, 16300, 77, 40),       # STL = 5, two tiles per wave, ragged last block with query-less waves
+                                          (8, 8, 8192, 96, 64),        # STL = 6, four tiles per wave: the three-register-set rotation wraps
+                                          (2, 8, 16384, 81, 32),       # STL = 6 with 15 masked slots, KS = 2 / DT = 1
+                                          (16, 8, 2048, 65, 48)])      # KS = 3 / DT = 2, 31 masked slots
+def test_attention_fused_register_resident_cross_kernel(B, H, Nq, Nk, d):
+    """attn_cross_kernel (K and V^T fragments in registers, no LDS) is taken only for 64 < Nk <= 96, d <= 64 and
+    ceil(Nq / 128) B H >= 2048: the Nk = 77 cases of test_attention_fused stay on the tiled kernel.  Tiles per wave by
+    launch_attn_cross (halved from 8 while ceil(Nq / (128 tpw)) B H < 1024): 2, 4, 2, 2.  One tile per wave cannot be reached through
+    the dispatcher at any shape: it needs ceil(Nq / 256) B H < 1024 while ceil(Nq / 128) B H >= 2048, and ceil(Nq / 128) <=
+    2 ceil(Nq / 256).  Reference: the fp64 softmax of _attn_ref_exp2 on the exact exponent q.k d^-1/2 log2(e), per sample on the device."""
+    ops = _ops()
+    assert 64 < Nk <= 96 and d <= 64 and (Nq + 127) // 128 * B * H >= 2048
+    Cc = H * d
+    q, k, v = r16(B * Nq, Cc, seed=140).cuda(), r16(B * Nk, Cc, seed=141).cuda(), r16(B * Nk, Cc, seed=142).cuda()
+    vt = ops.project_vt(v, torch.eye(Cc).half().cuda(), B, Nk, (Nk + 7) // 8 * 8)
+    out = ops.attention_fused(q, k, vt, B, H, Nq, Nk, d, d ** -0.5)
+    ref = torch.cat([_attn_ref_exp2(q[b * Nq:(b + 1) * Nq].double() * (d ** -0.5 * 1.4426950408889634), k[b * Nk:(b + 1) * Nk],
+                                    v[b * Nk:(b + 1) * Nk], 1, H, Nq, Nk, d) for b in range(B)])
+    e = rel_l2(out, ref)
+    assert torch.isfinite(out).all() and e < 2e-3, e
+
+
 @pytest.mark.parametrize("B,H,Nq,Nk,d", [(4, 8, 4096, 512, 40),       # MODE 1, two query tiles per wave, P.V on 16x16x32 MFMAs
                                           (4, 8, 4000, 333, 40),      # ... ragged last key tile, ragged query tile
                                           (1, 8, 1024, 1024, 40),     # MODE 1, one query tile per wave (too few blocks for the wide kernel)
