@@ -217,6 +217,11 @@ int icd_softmax_rows(const float* s, int64_t rows, int32_t cols, int32_t ld_s, f
  * out: [B, Nq, ldo].  d in {40, 64, 80, 160} (any multiple of 8 up to 160).  vt_batch_stride: elements between the V^T
  * blocks of consecutive samples (0 = H*d*ldvt; larger when vt is a row slice of a wider [B, sum(C), ldvt] buffer that
  * holds the V^T of every cross-attention layer).
+ * The pad columns [Nk, ldvt) of vt must be zero, or at least finite: the kernels multiply them with a probability that is exactly
+ * zero, so any finite pad gives the same bits and an Inf / NaN there poisons the row (icd_attention_masked does not need this: it
+ * masks the V^T fragment as well as the scores).
+ * Refused with ICD_ERR_INVALID before any launch: ldq, ldk or ldo below H*d, a non-zero vt_batch_stride below H*d*ldvt, q / k / vt not
+ * 16-byte aligned, out not 8-byte aligned (icd_attention_probs*: q / k / probs / acc 16-byte, the carries 8-byte).
  * Used on layers whose controller does not need P (utils/p2p.py:147,184-188: N > 32^2, or no controller). */
 int icd_attention_fused(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H, int32_t Nq,
                         int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,

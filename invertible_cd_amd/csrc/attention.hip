@@ -1078,6 +1078,10 @@ static int attention_probs_run(const void* q, const void* qc, const void* k, con
     ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldp % 8 == 0 && ldp >= Nk, "icd_attention_probs: leading dims must be 16-byte aligned, ldp >= Nk");
     ICD_CHECK_ARG(scale > 0.f, "icd_attention_probs: scale must be positive");
     ICD_CHECK_ARG((long long)B * H <= 65535, "icd_attention_probs: B * H exceeds the grid limit");
+    ICD_CHECK_ARG(ldq >= (long long)H * d && ldk >= (long long)H * d, "icd_attention_probs: ldq and ldk must be >= H * d");
+    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)probs) % 16 == 0 && ((uintptr_t)qc | (uintptr_t)kc) % 8 == 0,
+                  "icd_attention_probs: q, k and probs must be 16-byte aligned, the carries 8-byte");
+    ICD_CHECK_ARG(!epi || (uintptr_t)epi->acc % 16 == 0, "icd_attention_probs_ex: acc must be 16-byte aligned");
     ProbsK a;
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.p = (half_t*)probs;
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldp = ldp;
@@ -1153,6 +1157,11 @@ extern "C" int icd_attention_fused_ex(const void* q, const void* k, const void* 
     ICD_CHECK_ARG(d > 0 && d % 8 == 0 && d <= 160, "icd_attention_fused: head dim must be a multiple of 8, <= 160 (got %d)", d);
     ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Nk,
                   "icd_attention_fused: leading dims must be 16-byte aligned and ldvt >= Nk");
+    // (as icd_attention_masked: a sliced tensor with an odd element offset must be an error here, not a misaligned vector load there)
+    ICD_CHECK_ARG(ldq >= (long long)H * d && ldk >= (long long)H * d && ldo >= (long long)H * d, "icd_attention_fused: ldq, ldk and ldo must be >= H * d");
+    ICD_CHECK_ARG(vt_batch_stride == 0 || vt_batch_stride >= (int64_t)H * d * ldvt, "icd_attention_fused: vt_batch_stride below H * d * ldvt");
+    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) % 16 == 0 && (uintptr_t)out % 8 == 0,
+                  "icd_attention_fused: q, k and vt must be 16-byte aligned, out 8-byte");
     AttnK a;
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.out = (half_t*)out;
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
