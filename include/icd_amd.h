@@ -154,10 +154,13 @@ int icd_gemm(const icd_gemm_desc* d, void* stream);
 /* What icd_gemm would run for this descriptor (pure function of the descriptor; nothing is enqueued): kernel 0 = the 128-wide
  * tiles of gemm.hip, 1 = the 256-wide tiles of gemm_big.hip; tile_m x tile_n the block tile; ksplit > 1: split-K + reduce launch;
  * ln_inline: ICD_GEMM_LN_COMPUTE statistics come from the main loop's operand fragments (no statistics launch); xattn: the
- * cross-attention epilogue runs in this launch.  The executor records it per launch (icd_profile_dump) so that tests can assert
- * which code path a UNet forward took. */
+ * cross-attention epilogue runs in this launch; cfg: the big-tile configuration taken (0..6, the BIG_TILES rows of gemm_common.h -
+ * tiles of equal shape differ in their main loop; 100 / 101: the fused cross-attention launch on 256 x 256 / 192 x 256), -1 for the
+ * 128-wide tiles; group_m: m-tiles per L2 group of the block -> tile map the kernel receives.  The executor records it per launch
+ * (icd_profile_dump) so that tests can assert which code path a UNet forward took. */
 typedef struct {
     int32_t kernel, tile_m, tile_n, ksplit, ln_inline, xattn;
+    int32_t cfg, group_m;
 } icd_gemm_plan_info;
 int icd_gemm_plan(const icd_gemm_desc* d, icd_gemm_plan_info* out);
 /* Bytes of split-K scratch icd_gemm would like for this shape (0: the shape is not split). */

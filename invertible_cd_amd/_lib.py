@@ -68,7 +68,7 @@ class ProbsEpilogue(C.Structure):
 
 class GemmPlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32), ("ksplit", C.c_int32),
-                ("ln_inline", C.c_int32), ("xattn", C.c_int32)]
+                ("ln_inline", C.c_int32), ("xattn", C.c_int32), ("cfg", C.c_int32), ("group_m", C.c_int32)]
 
 
 class UNetConfig(C.Structure):

@@ -663,32 +663,44 @@ template <int MODE, bool TRANS, int WM, int NSTAGE, bool XATTN = false>
 int launch(const GemmK& k, int batch, hipStream_t st) {
     constexpr int smem = NSTAGE * (WM * 64 + BN) * 128;
     static std::atomic<unsigned long long> armed{0};
-    const int rc = icd_launch_lds(armed, "icd_gemm", &gemm_kernel<MODE, TRANS, WM, NSTAGE, XATTN>, dim3(k.nbm * k.nbn, k.ksplit, batch), dim3(WM * 128),
-                                  smem, st, k);
-    if (rc != ICD_OK) return rc;
-    if (k.ksplit > 1) return launch_reduce(k, st);
-    return ICD_OK;
+    return icd_launch_lds(armed, "icd_gemm", &gemm_kernel<MODE, TRANS, WM, NSTAGE, XATTN>, dim3(k.nbm * k.nbn, k.ksplit, batch), dim3(WM * 128),
+                          smem, st, k);
 }
 
 }  // namespace
 
-// Tile / split-K plan: 256x128 tiles when they fill the chip, otherwise 128x128; split K when the grid is still small
-// and K is deep.  Pure function of the shape (bit-reproducible results for a given shape).
+// icd_gemm in four steps: gemm_validate refuses, gemm_plan decides (pure: what icd_gemm_plan reports), gemm_args fills the kernels' argument
+// struct, gemm_launch enqueues.  All tuning / diagnostics inputs travel in the descriptor: the library keeps no process-wide GEMM state.
+enum class Tile { Dense128, ConvFast, ConvGeneral, XattnHost, Big };      // gemm_kernel<0 | 1 | 2 | 0 with XATTN>, launch_big(cfg)
+struct GemmPlan {          // (default member initialisers: a new field names its own default, gemm_plan starts from GemmPlan{})
+    Tile family = Tile::Dense128;
+    int cfg = -1, wm = 2;                        // cfg: BIG_TILES index or XATTN_TILE_256 / _192 (Big), else -1; wm: 2 / 4 = 128 / 256 rows (128-wide kernels)
+    int tile_m = 128, tile_n = 128, nbm = 0, nbn = 0, gm = 1, ksplit = 1, kt_per_split = 0, batch = 1;
+    bool ln_inline = false;                      // ICD_GEMM_LN_COMPUTE: the tile takes the statistics in its main loop ...
+    bool ln_stats_pass = false;                  // ... or an icd_layernorm_stats launch runs in front of it
+};
+
+// Split-K depth, for every plan and icd_gemm_workspace_bytes: at most `want` and 8 splits, >= 8 k-tiles per split, fp32 partials [s][M][N] that fit
+static int split_depth(int want, int nk, int M, int N, long long ws_bytes) {
+    int s = want > 8 ? 8 : want;
+    while (s > 1 && nk / s < 8) --s;
+    while (s > 1 && (long long)s * M * N * 4 > ws_bytes) --s;
+    return s < 1 ? 1 : s;
+}
+static int splits_to_fill(long long blocks) { return (int)((256 + blocks - 1) / blocks); }      // ... that bring `blocks` to one round of the chip
+static void set_split(GemmPlan* p, int nk, int s) {          // no empty splits
+    p->kt_per_split = (nk + s - 1) / s; p->ksplit = (nk + p->kt_per_split - 1) / p->kt_per_split;
+}
+
+// Tile / split-K plan of the 128-wide kernels: 256x128 tiles when they fill the chip, otherwise 128x128; split K when the grid is still
+// small and K is deep.  Pure function of the shape (bit-reproducible results for a given shape).
 static void plan_gemm(int M, int N, int K, int batch, bool allow_split, long long ws_bytes, int* wm, int* ksplit) {
     const int nbn = (N + 127) / 128, nk = (K + 63) / 64;
     const long long b256 = (long long)((M + 255) / 256) * nbn * batch;
     const long long b128 = (long long)((M + 127) / 128) * nbn * batch;
-    *ksplit = 1;
-    if (b256 >= 200 || (M >= 256 && nk >= 32 && allow_split)) *wm = 4;
-    else *wm = 2;
+    *wm = b256 >= 200 || (M >= 256 && nk >= 32 && allow_split) ? 4 : 2;
     const long long blocks = *wm == 4 ? b256 : b128;
-    if (allow_split && blocks < 160 && nk >= 16) {
-        int s = (int)((256 + blocks - 1) / blocks);
-        s = s > 8 ? 8 : s;
-        while (s > 1 && nk / s < 8) --s;
-        while (s > 1 && (long long)s * M * N * 4 > ws_bytes) --s;
-        *ksplit = s < 1 ? 1 : s;
-    }
+    *ksplit = allow_split && blocks < 160 && nk >= 16 ? split_depth(splits_to_fill(blocks), nk, M, N, ws_bytes) : 1;
 }
 
 extern "C" int64_t icd_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K) {
@@ -699,275 +711,263 @@ extern "C" int64_t icd_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K) {
     for (int tn = 4; tn <= 5; ++tn) {                                         // the big-tile plans may split deeper
         if ((tn == 5 && N % 320 != 0) || (tn == 4 && N % 256 != 0) || M < 256 || K % 64 != 0) continue;
         const long long blocks = (long long)((M + 255) / 256) * (N / (64 * tn));
-        if (blocks < 192 && nk >= 16) {
-            int s = (int)((256 + blocks - 1) / blocks);
-            s = s > 8 ? 8 : s;
-            while (s > 1 && nk / s < 8) --s;
-            if (s > 1) need = std::max<int64_t>(need, (int64_t)s * M * N * 4);
-        }
+        const int s = blocks < 192 && nk >= 16 ? split_depth(splits_to_fill(blocks), nk, M, N, 1LL << 60) : 1;
+        if (s > 1) need = std::max<int64_t>(need, (int64_t)s * M * N * 4);
     }
     return need;
 }
 
-// One planner for icd_gemm (launch = true) and icd_gemm_plan (launch = false: reports the tile the same call would run on, nothing
-// is enqueued).  All tuning / diagnostics inputs travel in the descriptor: the library keeps no process-wide GEMM state.
-static int gemm_run(const icd_gemm_desc* d, void* stream, icd_gemm_plan_info* info, bool do_launch) {
+static int conv_taps(const icd_gemm_desc* d) { return d->conv_ktaps || d->out_remap_w ? 4 : d->ksize * d->ksize; }
+static unsigned orm_magic_of(unsigned W) { return (unsigned)((0x100000000ULL + W - 1) / W); }   // floor(m / W) = umulhi(m, magic) for m * (magic W - 2^32) < 2^32
+static bool conv_aligned(const icd_gemm_desc* d) { return (d->C0 + d->C1) % 64 == 0 && d->C0 % 64 == 0; }   // whole 64-channel chunks: the fast loaders
 
+// Every refusal that does not depend on the tile taken (those two are in gemm_plan): before anything is decided, written or enqueued.
+static int gemm_validate(const icd_gemm_desc* d) {
     ICD_CHECK_ARG(d != nullptr, "icd_gemm: null descriptor");
     ICD_CHECK_ARG(d->a0 && d->w && d->out, "icd_gemm: a0/w/out must be non-null");
     ICD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "icd_gemm: M,N,K must be positive (got %d,%d,%d)", d->M, d->N, d->K);
     ICD_CHECK_ARG(d->K % 8 == 0 && d->ldw % 8 == 0, "icd_gemm: K and ldw must be multiples of 8 (K=%d ldw=%d)", d->K, d->ldw);
     ICD_CHECK_ARG(d->N % 8 == 0, "icd_gemm: N must be a multiple of 8 (got %d)", d->N);
     ICD_CHECK_ARG(d->mode == 0 || d->mode == 1, "icd_gemm: mode must be 0 (dense) or 1 (conv)");
-    const bool trans = d->flags & ICD_GEMM_OUT_TRANS;
-    const bool geglu = d->flags & ICD_GEMM_GEGLU;
-    ICD_CHECK_ARG(!(trans && (geglu || (d->flags & ICD_GEMM_OUT_F32) || d->bias || d->resid || d->rowbias)),
-                  "icd_gemm: transposed output supports alpha (and the fused LayerNorm) only");
-    ICD_CHECK_ARG(!(geglu && (d->resid || d->rowbias || (d->flags & ICD_GEMM_OUT_F32) || d->N % 64 != 0)),
-                  "icd_gemm: GEGLU needs N %% 64 == 0 and no resid/rowbias/f32 output");
+    const bool trans = d->flags & ICD_GEMM_OUT_TRANS, geglu = d->flags & ICD_GEMM_GEGLU, f32 = d->flags & ICD_GEMM_OUT_F32;
+    ICD_CHECK_ARG(!(trans && (geglu || f32 || d->bias || d->resid || d->rowbias)), "icd_gemm: transposed output supports alpha (and the fused LayerNorm) only");
+    ICD_CHECK_ARG(!(geglu && (d->resid || d->rowbias || f32 || d->N % 64 != 0)), "icd_gemm: GEGLU needs N %% 64 == 0 and no resid/rowbias/f32 output");
     if (d->rowbias || trans) ICD_CHECK_ARG(d->rows_per_sample > 0, "icd_gemm: rows_per_sample required");
-    GemmK k;
-    k.a0 = (const half_t*)d->a0; k.a1 = (const half_t*)d->a1; k.w = (const half_t*)d->w;
-    k.bias = d->bias; k.rowbias = (const half_t*)d->rowbias; k.resid = (const half_t*)d->resid; k.out = d->out;
-    k.partial = (float*)d->splitk_ws;
-    k.M = d->M; k.N = d->N; k.K = d->K; k.Nw = d->Nw > 0 ? d->Nw : d->N;
-    k.lda = d->lda; k.ldw = d->ldw; k.ldo = d->ldo; k.ldr = d->ldr; k.ld_rowbias = d->ld_rowbias;
-    k.rps = d->rows_per_sample > 0 ? d->rows_per_sample : 1;
-    k.C0 = d->C0; k.C1 = d->C1; k.Hin = d->Hin; k.Win = d->Win; k.Hout = d->Hout; k.Wout = d->Wout;
-    k.ksize = d->ksize; k.stride = d->stride; k.upsample = d->upsample;
-    int ktaps = d->ksize * d->ksize;
-    k.tapmap = 0x876543210ULL | ((unsigned long long)ktaps << 60);
-    k.orm_pack = 1; k.orm_magic = 0;
-    if (d->conv_ktaps || d->out_remap_w) {
-        // phase form of the upsampling conv (icd_amd.h): 4 of the 9 taps on the input grid, output rows scattered to one pixel phase
+    if (d->conv_ktaps || d->out_remap_w) {          // phase form of the upsampling conv (icd_amd.h): 4 of the 9 taps, rows scattered to one pixel phase
         ICD_CHECK_ARG(d->mode == 1 && d->ksize == 3 && d->stride == 1 && d->upsample == 0 && d->conv_ktaps == 4 && !(d->flags & ICD_GEMM_PAD_HI),
                       "icd_gemm: conv_ktaps = 4 goes with a stride-1 3x3 geometry without upsample");
         ICD_CHECK_ARG(d->conv_tap_base == 0 || d->conv_tap_base == 1 || d->conv_tap_base == 3 || d->conv_tap_base == 4,
                       "icd_gemm: conv_tap_base must be 3 py + px, py / px in {0, 1}");
         ICD_CHECK_ARG(d->out_remap_w == 0 || (d->out_remap_w == d->Wout && !trans && !geglu && !d->resid && !d->out_f32 && d->batch <= 1),
                       "icd_gemm: out_remap_w must equal Wout (plain fp16 / fp32 output, no residual)");
-        ktaps = 4;
-        { const unsigned long long t0 = (unsigned long long)d->conv_tap_base; k.tapmap = t0 | ((t0 + 1) << 4) | ((t0 + 3) << 8) | ((t0 + 4) << 12) | (4ULL << 60); }
         if (d->out_remap_w) {
-            const unsigned W = (unsigned)d->out_remap_w;
+            const unsigned long long W = (unsigned)d->out_remap_w;
             ICD_CHECK_ARG(W >= 2 && W < 8192 && d->out_remap_c >= 0 && d->out_remap_c < 32768, "icd_gemm: out_remap_w must be 2 .. 8191");
-            k.orm_pack = 2u | ((2u * W) << 2) | ((unsigned)d->out_remap_c << 17);
-            k.orm_magic = (unsigned)((0x100000000ULL + W - 1) / W);             // floor(m / W) = umulhi(m, magic) for m * (magic W - 2^32) < 2^32
-            ICD_CHECK_ARG((unsigned long long)d->M * (unsigned long long)((unsigned long long)k.orm_magic * W - 0x100000000ULL) < 0x100000000ULL,
+            ICD_CHECK_ARG((unsigned long long)d->M * (orm_magic_of((unsigned)W) * W - 0x100000000ULL) < 0x100000000ULL,
                           "icd_gemm: out_remap_w: M too large for the row map");
         }
     }
-    k.zdiv = d->zdiv > 0 ? d->zdiv : 1;
-    k.a_bs0 = d->a_bs0; k.a_bs1 = d->a_bs1; k.w_bs0 = d->w_bs0; k.w_bs1 = d->w_bs1; k.o_bs0 = d->o_bs0; k.o_bs1 = d->o_bs1;
-    k.alpha = d->alpha; k.flags = d->flags;
-    k.timeline = (unsigned long long*)d->debug_timeline;
-    k.out32 = d->out_f32;
-    ICD_CHECK_ARG(!(d->out_f32 && (trans || geglu || (d->flags & ICD_GEMM_OUT_F32) || d->batch > 1 || d->xattn_k)),
-                  "icd_gemm: out_f32 (second fp32 output) goes with a plain fp16 output only");
-    k.resid_c = (const unsigned char*)d->resid_carry; k.out_c = (unsigned char*)d->out_carry;
-    ICD_CHECK_ARG(!(d->out_carry && (trans || geglu || (d->flags & ICD_GEMM_OUT_F32) || d->batch > 1 || d->xattn_k)),
-                  "icd_gemm: out_carry (error carry of the output) goes with a plain fp16 output only");
-    ICD_CHECK_ARG(!(d->resid_carry && (!d->resid || (d->flags & ICD_GEMM_RESID_F32) || d->batch > 1)),
-                  "icd_gemm: resid_carry needs an fp16 resid (unbatched)");
+    const bool plain = !(trans || geglu || f32 || d->batch > 1 || d->xattn_k);
+    ICD_CHECK_ARG(!d->out_f32 || plain, "icd_gemm: out_f32 (second fp32 output) goes with a plain fp16 output only");
+    ICD_CHECK_ARG(!d->out_carry || plain, "icd_gemm: out_carry (error carry of the output) goes with a plain fp16 output only");
+    ICD_CHECK_ARG(!(d->resid_carry && (!d->resid || (d->flags & ICD_GEMM_RESID_F32) || d->batch > 1)), "icd_gemm: resid_carry needs an fp16 resid (unbatched)");
     ICD_CHECK_ARG(!((d->out_carry && d->ldo % 8 != 0) || (d->resid_carry && d->ldr % 8 != 0)),
                   "icd_gemm: carried tensors need leading dimensions that are multiples of 8");
-    const int g_group_m = d->tune_group_m, g_xattn_tile = d->tune_xattn_tile;
-    k.gm = g_group_m > 0 ? g_group_m : 1;        // the planner widens it below for launches with many n-tiles
-    k.ln_stats = d->ln_stats; k.ln_s = d->ln_colsum;
-    k.ln_stats_w = nullptr; k.ln_eps = d->ln_eps > 0.f ? d->ln_eps : 1e-5f;
-    // ICD_GEMM_LN_COMPUTE: the big tiles compute the statistics in their main loop; every other path runs the statistics launch
-    const bool ln_compute = (d->flags & ICD_GEMM_LN_COMPUTE) != 0;
-    ICD_CHECK_ARG(!ln_compute || d->ln_stats, "icd_gemm: ICD_GEMM_LN_COMPUTE needs the ln_stats buffer (and ln_colsum)");
-    auto plan_is = [&](int kernel, int tm, int tn, int xattn) {      // report the choice; true: planning only, do not launch
-        if (info) {
-            info->kernel = kernel; info->tile_m = tm; info->tile_n = tn; info->ksplit = k.ksplit;
-            info->ln_inline = k.ln_stats_w != nullptr; info->xattn = xattn;
-        }
-        return !do_launch;
-    };
-    auto ln_stats_launch = [&]() -> int {
-        if (!ln_compute || !do_launch) return ICD_OK;
-        ICD_CHECK_ARG(d->lda == d->K, "icd_gemm: ICD_GEMM_LN_COMPUTE on this path needs contiguous rows (lda == K)");
-        return icd_layernorm_stats(d->a0, d->M, d->K, k.ln_eps, const_cast<float*>(d->ln_stats), stream);
-    };
+    ICD_CHECK_ARG(!(d->flags & ICD_GEMM_LN_COMPUTE) || d->ln_stats, "icd_gemm: ICD_GEMM_LN_COMPUTE needs the ln_stats buffer (and ln_colsum)");
     ICD_CHECK_ARG((d->ln_stats == nullptr) == (d->ln_colsum == nullptr), "icd_gemm: ln_stats and ln_colsum go together");
-    ICD_CHECK_ARG(!(d->ln_stats && (d->mode != 0 || (d->batch > 1) || (d->flags & ICD_GEMM_OUT_F32))),
-                  "icd_gemm: the fused LayerNorm applies to dense, unbatched, fp16-output GEMMs");
-    const int batch = d->batch > 0 ? d->batch : 1;
-    k.xk = (const half_t*)d->xattn_k; k.xvt = (const half_t*)d->xattn_vt;
-    k.x_nk = d->xattn_nk; k.x_ldk = d->xattn_ldk; k.x_ldvt = d->xattn_ldvt; k.x_vt_bs = d->xattn_vt_bs;
-    k.x_scale_log2 = d->xattn_scale * ATTN_LOG2E;
-    if (d->xattn_k) {
-        // query projection + cross-attention in one launch: out = softmax(scale (A W^T + ...) K^T) V per 64-wide head
+    ICD_CHECK_ARG(!(d->ln_stats && (d->mode != 0 || (d->batch > 1) || f32)), "icd_gemm: the fused LayerNorm applies to dense, unbatched, fp16-output GEMMs");
+    if (d->xattn_k) {          // query projection + cross-attention in one launch: out = softmax(scale (A W^T + ...) K^T) V per 64-wide head
         ICD_CHECK_ARG(d->xattn_vt && d->xattn_scale > 0.f, "icd_gemm(xattn): xattn_vt and a positive xattn_scale are required");
-        ICD_CHECK_ARG(d->mode == 0 && batch == 1 && !(d->flags & (ICD_GEMM_GEGLU | ICD_GEMM_OUT_F32 | ICD_GEMM_OUT_TRANS)) &&
-                      !d->resid && !d->rowbias, "icd_gemm(xattn): dense fp16 GEMM without residual / rowbias / GEGLU only");
+        ICD_CHECK_ARG(d->mode == 0 && d->batch <= 1 && !geglu && !f32 && !trans && !d->resid && !d->rowbias,
+                      "icd_gemm(xattn): dense fp16 GEMM without residual / rowbias / GEGLU only");
         ICD_CHECK_ARG(d->N % 128 == 0 && d->K % 64 == 0 && d->lda % 8 == 0 && d->ldo % 8 == 0,
                       "icd_gemm(xattn): N %% 128, K %% 64 and 16-byte aligned leading dims required (head dim 64)");
         ICD_CHECK_ARG(d->rows_per_sample > 0 && d->rows_per_sample % 256 == 0 && d->M % d->rows_per_sample == 0,
                       "icd_gemm(xattn): rows_per_sample must be a multiple of 256 (a 256-row tile stays inside one sample)");
         ICD_CHECK_ARG(d->xattn_nk > 0 && d->xattn_nk <= 96 && d->xattn_ldk % 4 == 0 && d->xattn_ldvt % 8 == 0 && d->xattn_ldvt >= d->xattn_nk,
                       "icd_gemm(xattn): 1..96 keys, ldk %% 4 == 0, ldvt %% 8 == 0, ldvt >= keys");
-        k.ksplit = 1; k.kt_per_split = (d->K + BK - 1) / BK;
-        // 128 x 128 tiles with two resident blocks per CU (measured, SDXL 32x32 level: 63.8 us at B = 8 / 98.9 us at B = 16 against
-        // 73.8 / 113.1 us with 256 x 128 tiles, whose partial last round costs a whole tile; the two launches it replaces take
-        // 67.3 / 109.9 us); the 256-row tile stays available for tuning
-        // ... and since the 256 x 256 tile of gemm_big.hip hosts it (a block = 256 queries x 4 heads, K / V^T staged once in the
-        // idle operand stages): the fast GEMM tile under the same epilogue, LayerNorm statistics from its own main loop
-        if ((g_xattn_tile == 0 || g_xattn_tile == 5 || g_xattn_tile == 6) && d->N % 256 == 0 && (long long)(d->M / 256) * (d->N / 256) >= 32) {
-            // 256 or 192 query rows per block: the 192-row tile lays ceil(rps / 192) m-tiles over every sample (the last one partial), which
-            // turns the 160 blocks of SDXL's 1024-token layers at 8 images per GPU into 240 - one round on 256 CUs either way, of blocks
-            // with 3/4 of the work.  Whichever needs less (rounds x rows per block); tune_xattn_tile 5 / 6 force 256 / 192 (A/B)
-            const long long nb = d->N / 256, b256 = (long long)(d->M / 256) * nb;
-            const int bps192 = (d->rows_per_sample + 191) / 192;
-            const long long b192 = (long long)(d->M / d->rows_per_sample) * bps192 * nb;
-            const long long t256 = (b256 + 255) / 256 * 256, t192 = (b192 + 255) / 256 * 192;
-            const bool t192_wins = g_xattn_tile == 6 || (g_xattn_tile == 0 && t192 < t256);
-            k.nbm = t192_wins ? (d->M / d->rows_per_sample) * bps192 : d->M / 256; k.nbn = d->N / 256;
-            if (ln_compute && k.nbn <= 12 && !(d->flags & ICD_GEMM_TUNE_NO_LN_INLINE)) k.ln_stats_w = const_cast<float*>(d->ln_stats);
-            else { const int rc = ln_stats_launch(); if (rc != ICD_OK) return rc; }
-            if (plan_is(1, t192_wins ? 192 : 256, 256, 1)) return ICD_OK;
-            return launch_big(k, t192_wins ? 101 : 100, (hipStream_t)stream);
-        }
-        const bool big = g_xattn_tile == 4;
-        k.nbm = d->M / (big ? 256 : 128); k.nbn = d->N / 128;
-        if (g_group_m <= 0 && k.nbn >= 16) k.gm = 8;
-        { const int rc = ln_stats_launch(); if (rc != ICD_OK) return rc; }
-        if (plan_is(0, big ? 256 : 128, 128, 1)) return ICD_OK;
-        return big ? launch<0, false, 4, 3, true>(k, 1, (hipStream_t)stream) : launch<0, false, 2, 2, true>(k, 1, (hipStream_t)stream);
     }
-    int wm = 2, ks = 1;
-    const bool allow_split = !trans && !geglu && batch == 1 && d->splitk_ws != nullptr && d->splitk_ws_bytes > 0;
-    const int nk_total = (d->K + BK - 1) / BK;
-    hipStream_t st = (hipStream_t)stream;
-    // ---- high-intensity tiles (gemm_big.hip), chosen from BIG_TILES by the cost model below ------------------------
-    {
-        // (the big conv tiles address their sources with 32-bit buffer offsets whose bit 31 marks a zero-padding read: < 2 GiB per source
-        // tensor, else the 128-wide kernels)
-        // (sample count from the output geometry, as the kernel derives its descriptor size - not from rows_per_sample, which a caller
-        // may leave unset; the geometry itself is validated before any tile is chosen)
-        if (d->mode == 1) {
-            ICD_CHECK_ARG(d->ksize == 1 || d->ksize == 3, "icd_gemm: conv ksize must be 1 or 3");
-            ICD_CHECK_ARG(d->stride == 1 || d->stride == 2, "icd_gemm: conv stride must be 1 or 2");
-            ICD_CHECK_ARG(d->upsample == 0 || d->upsample == 1, "icd_gemm: upsample must be 0 or 1");
-            ICD_CHECK_ARG(d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->M % (d->Hout * d->Wout) == 0,
-                          "icd_gemm: bad conv geometry");
-        }
-        const long long conv_hw = d->mode == 1 ? (long long)d->Hout * d->Wout : 0;
-        const long long conv_src_bytes = conv_hw > 0 ? ((d->M + conv_hw - 1) / conv_hw) * d->Hin * d->Win * std::max(d->C0, d->C1) * 2 : 0;
-        const bool conv_fast = d->mode == 1 && ((d->C0 + d->C1) % 64 == 0) && (d->C0 % 64 == 0) && conv_src_bytes < (1LL << 31) - (1 << 22);
-        // transposed (V^T) outputs take the big tiles when a 32-row tile never straddles two samples and no pad columns
-        // have to be zeroed (ldo == rows_per_sample); otherwise the 128-wide kernel's general epilogue handles them
-        const bool trans_ok = !trans || (d->rows_per_sample % 32 == 0 && d->M % 32 == 0 && d->ldo == d->rows_per_sample);
-        const bool base_ok = batch == 1 && trans_ok && (d->mode == 0 || conv_fast) && d->M >= 256 && (d->Nw <= 0 || d->Nw >= d->N) &&
-                             (d->K % 64 == 0) && !(d->flags & ICD_GEMM_TUNE_NO_BIG);
-        // Cost model in units of "one k-tile of a 256x256 block" (calibrated with tools/gemm_bench.py, same-box A/B):
-        // a block owns its CU, so a launch costs rounds x (k-tiles x tk + fixed), fixed = prologue + exposed epilogue.
-        int cfg = -1, s = 1;
-        double best = 1e30, best_fill = 0.0, best_ok = 1e30, fill_ok = 0.0;
-        int cfg_ok = -1;
-        const int forced = ((d->flags >> 24) & 15) - 1;          // ICD_GEMM_TUNE_BIG_CFG(i)
-        for (int ci = 0; ci < NUM_BIG_TILES && base_ok; ++ci) {
-            const BigTile& c = BIG_TILES[ci];
-            if (forced >= 0 && ci != forced) continue;
-            // (the 192-row ping-pong tile serves the dense M = 8192-class layers; as a conv tile it measured 7 % behind the 256 x 320 one on
-            //  8192 x 1280 x 11520 / 17280 - more operand bytes per flop - and is taken for convs only when forced)
-            if (ci == PP192_TILE && d->mode == 1 && forced != ci) continue;
-            if ((ci == PP_TILE || ci == PP320_TILE || ci == PP192_TILE) && (!pp_operands_ok(k, d->mode == 1) || (d->flags & ICD_GEMM_TUNE_NO_PP))) continue;
-            if (d->N % c.bn != 0 || (geglu && !c.geglu_ok) || ((d->flags & ICD_GEMM_TUNE_BN256) && c.bn != 256)) continue;
-            const long long b0 = (long long)((d->M + c.bm - 1) / c.bm) * (d->N / c.bn);
-            int smax = 1;
-            if (allow_split && b0 < 192 && nk_total >= 16) {
-                smax = 8;
-                while (smax > 1 && nk_total / smax < 8) --smax;
-                while (smax > 1 && (long long)smax * d->M * d->N * 4 > d->splitk_ws_bytes) --smax;
-            }
-            for (int sx = 1; sx <= smax; ++sx) {
-                const long long bt = b0 * sx;
-                const long long full = bt / 256, rem = bt % 256;
-                // rounds are strict for the first two (all blocks in lockstep), later ones desynchronise
-                const double rounds = bt <= 512 ? (double)((bt + 255) / 256) : (double)full + (rem ? 0.3 + 0.7 * rem / 256.0 : 0.0);
-                const double act = bt >= 256 ? 256.0 : (double)bt;
-                const double w = act <= 160 ? 0.0 : act >= 200 ? 1.0 : (act - 160) / 40.0;
-                const double tk = c.tk_part + w * (c.tk_full - c.tk_part);
-                const int kps = (nk_total + sx - 1) / sx;
-                double cost = rounds * (kps * tk + c.fixed);
-                if (sx > 1) cost += (double)(sx + 1) * d->M * d->N * 4.0 / 3.5e12 / 1.5e-6 + 4.0;   // fp32 partials + reduce launch
-                // (round 6: the cheapest candidate is picked as before and the launch goes to the 128-wide kernels when it fills its last round
-                //  below 45 % - UNLESS an un-split candidate fills well: 2048 x 2560 x 1280 lost its 128 x 320 tile (128 blocks) to the 128 x 128
-                //  kernel the day a cheaper-looking 192 x 256 entry (110 blocks) appeared.  Split-K candidates are not rescued this way: 2048 x 1280
-                //  x 1280 on 128 x 320 split 2 measured 26.2 us against 17.9 on the 128 x 128 kernel.)
-                const double fill = (double)bt / (double)(((bt + 255) / 256) * 256);
-                if (fill >= 0.45 && sx == 1 && cost < best_ok) { best_ok = cost; cfg_ok = ci; fill_ok = fill; }
-                if (cost < best) { best = cost; cfg = ci; s = sx; best_fill = fill; }
-            }
-        }
-        if (cfg >= 0 && best_fill < 0.45 && forced < 0 && !(d->flags & ICD_GEMM_TUNE_FORCE_BIG) && cfg_ok >= 0) { cfg = cfg_ok; s = 1; best_fill = fill_ok; }
-        if (cfg >= 0 && (best_fill >= 0.45 || forced >= 0 || (d->flags & ICD_GEMM_TUNE_FORCE_BIG))) {
-            const BigTile& c = BIG_TILES[cfg];
-            k.nbm = (d->M + c.bm - 1) / c.bm; k.nbn = d->N / c.bn;
-            if (g_group_m <= 0 && k.nbn >= 16) k.gm = 8;        // measured: +5 % on N = 10240 (40 n-tiles), nothing to gain on few n-tiles
-            k.kt_per_split = (nk_total + s - 1) / s;
-            k.ksplit = (nk_total + k.kt_per_split - 1) / k.kt_per_split;
-            if (d->mode == 1) {
-                ICD_CHECK_ARG(d->ksize == 1 || d->ksize == 3, "icd_gemm: conv ksize must be 1 or 3");
-                ICD_CHECK_ARG(d->K == ktaps * (d->C0 + d->C1), "icd_gemm: K != taps*Cin");
-                ICD_CHECK_ARG((d->C1 == 0) == (d->a1 == nullptr), "icd_gemm: a1/C1 mismatch");
-            } else {
-                k.ksize = 0; k.Hout = 0;
-                ICD_CHECK_ARG(d->lda % 8 == 0, "icd_gemm: lda must be a multiple of 8");
-            }
-            if (ln_compute) {
-                // every n-tile recomputes the statistics of its rows (a few % of its main loop): free up to ~10 n-tiles (to_q / to_qk:
-                // 65.1 vs 65.7 us at 8192 x 2560 x 1280), dearer than the 8 us statistics launch on the 40 n-tiles of a GEGLU
-                // projection (243.9 vs 229.5 + 8)
-                const bool inline_ok = d->mode == 0 && k.ksplit == 1 && !trans && !(d->flags & (ICD_GEMM_OUT_F32 | ICD_GEMM_RESID_F32)) &&
-                                       !(d->flags & ICD_GEMM_TUNE_NO_LN_INLINE) && k.nbn <= 12 && !d->out_carry && !d->resid_carry;
-                if (inline_ok) k.ln_stats_w = const_cast<float*>(d->ln_stats);
-                else { const int rc0 = ln_stats_launch(); if (rc0 != ICD_OK) return rc0; }
-            }
-            if (plan_is(1, c.bm, c.bn, 0)) return ICD_OK;
-            const int rc = launch_big(k, cfg, st);
-            if (rc != ICD_OK) return rc;
-            if (k.ksplit > 1) return launch_reduce(k, st);
-            return ICD_OK;
-        }
-    }
-    { const int rc = ln_stats_launch(); if (rc != ICD_OK) return rc; }
-    plan_gemm(d->M, d->N, d->K, batch, allow_split, d->splitk_ws_bytes, &wm, &ks);
-    if (d->flags & ICD_GEMM_TUNE_WM2) { wm = 2; ks = 1; }          // tuning overrides (tools/gemm_bench.py)
-    if (d->flags & ICD_GEMM_TUNE_WM4) { wm = 4; ks = 1; }
-    k.ksplit = ks;
-    k.kt_per_split = (nk_total + ks - 1) / ks;
-    k.ksplit = (nk_total + k.kt_per_split - 1) / k.kt_per_split;      // no empty splits
-    k.nbm = (d->M + wm * 64 - 1) / (wm * 64); k.nbn = (d->N + BN - 1) / BN;
-    if (g_group_m <= 0 && k.nbn >= 16) k.gm = 8;
     if (d->mode == 1) {
         ICD_CHECK_ARG(d->ksize == 1 || d->ksize == 3, "icd_gemm: conv ksize must be 1 or 3");
         ICD_CHECK_ARG(d->stride == 1 || d->stride == 2, "icd_gemm: conv stride must be 1 or 2");
         ICD_CHECK_ARG(d->upsample == 0 || d->upsample == 1, "icd_gemm: upsample must be 0 or 1");
         ICD_CHECK_ARG(d->C0 > 0 && d->C0 % 8 == 0 && d->C1 % 8 == 0 && d->C1 >= 0, "icd_gemm: conv channels must be multiples of 8");
         ICD_CHECK_ARG((d->C1 == 0) == (d->a1 == nullptr), "icd_gemm: a1/C1 mismatch");
-        ICD_CHECK_ARG(d->K == ktaps * (d->C0 + d->C1), "icd_gemm: K != taps*Cin");
-        ICD_CHECK_ARG(d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->M % (d->Hout * d->Wout) == 0,
-                      "icd_gemm: bad conv geometry");
-        ICD_CHECK_ARG(batch == 1 && !trans, "icd_gemm: conv mode is not batched / transposed");
-        const bool fast = ((d->C0 + d->C1) % 64 == 0) && (d->C0 % 64 == 0);
-        if (!fast) k.nbm = (d->M + 127) / 128;
-        if (plan_is(0, fast && wm == 4 ? 256 : 128, 128, 0)) return ICD_OK;
-        if (!fast) return launch<2, false, 2, 2>(k, 1, st);
-        return wm == 4 ? launch<1, false, 4, 3>(k, 1, st) : launch<1, false, 2, 2>(k, 1, st);
+        ICD_CHECK_ARG(d->K == conv_taps(d) * (d->C0 + d->C1), "icd_gemm: K != taps*Cin");
+        ICD_CHECK_ARG(d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->M % (d->Hout * d->Wout) == 0, "icd_gemm: bad conv geometry");
+    } else {
+        ICD_CHECK_ARG(d->lda % 8 == 0, "icd_gemm: lda must be a multiple of 8");
     }
-    ICD_CHECK_ARG(d->lda % 8 == 0, "icd_gemm: lda must be a multiple of 8");
-    if (plan_is(0, wm * 64, 128, 0)) return ICD_OK;
-    if (trans) return wm == 4 ? launch<0, true, 4, 3>(k, batch, st) : launch<0, true, 2, 2>(k, batch, st);
-    return wm == 4 ? launch<0, false, 4, 3>(k, batch, st) : launch<0, false, 2, 2>(k, batch, st);
+    return ICD_OK;
 }
 
-extern "C" int icd_gemm(const icd_gemm_desc* d, void* stream) { return gemm_run(d, stream, nullptr, true); }
+static bool split_allowed(const icd_gemm_desc* d) {
+    return !(d->flags & (ICD_GEMM_OUT_TRANS | ICD_GEMM_GEGLU)) && d->batch <= 1 && d->splitk_ws != nullptr && d->splitk_ws_bytes > 0;
+}
+// m-tiles per L2 group: measured +5 % on N = 10240 (40 n-tiles) with 8, nothing to gain on few n-tiles
+static int group_m(const icd_gemm_desc* d, int nbn) { return d->tune_group_m > 0 ? d->tune_group_m : nbn >= 16 ? 8 : 1; }
+
+// The high-intensity tile (gemm_big.hip) of a launch, from BIG_TILES by the cost model below: its index and the split depth in *split,
+// or -1 for the 128-wide kernels.
+static int pick_big_tile(const icd_gemm_desc* d, int* split) {
+    const bool trans = d->flags & ICD_GEMM_OUT_TRANS, geglu = d->flags & ICD_GEMM_GEGLU, conv = d->mode == 1;
+    const int forced = ((d->flags >> 24) & 15) - 1;          // ICD_GEMM_TUNE_BIG_CFG(i)
+    const bool force = forced >= 0 || (d->flags & ICD_GEMM_TUNE_FORCE_BIG);
+    const int nk_total = (d->K + BK - 1) / BK;
+    *split = 1;
+    // (the big conv tiles address their sources with 32-bit buffer offsets whose bit 31 marks a zero-padding read: < 2 GiB per source
+    // tensor, else the 128-wide kernels; sample count from the output geometry, as the kernel derives its descriptor size - not from
+    // rows_per_sample, which a caller may leave unset)
+    const long long conv_hw = conv ? (long long)d->Hout * d->Wout : 0;
+    const long long conv_src_bytes = conv ? ((d->M + conv_hw - 1) / conv_hw) * d->Hin * d->Win * std::max(d->C0, d->C1) * 2 : 0;
+    const bool conv_fast = conv && conv_aligned(d) && conv_src_bytes < (1LL << 31) - (1 << 22);
+    // transposed (V^T) outputs take the big tiles when a 32-row tile never straddles two samples and no pad columns
+    // have to be zeroed (ldo == rows_per_sample); otherwise the 128-wide kernel's general epilogue handles them
+    const bool trans_ok = !trans || (d->rows_per_sample % 32 == 0 && d->M % 32 == 0 && d->ldo == d->rows_per_sample);
+    const bool base_ok = d->batch <= 1 && trans_ok && (!conv || conv_fast) && d->M >= 256 && (d->Nw <= 0 || d->Nw >= d->N) &&
+                         (d->K % 64 == 0) && !(d->flags & ICD_GEMM_TUNE_NO_BIG);
+    GemmK o = {};                                            // what pp_operands_ok looks at
+    o.M = d->M; o.K = d->K; o.Nw = d->Nw > 0 ? d->Nw : d->N; o.lda = d->lda; o.ldw = d->ldw;
+    const bool pp_ok = pp_operands_ok(o, conv) && !(d->flags & ICD_GEMM_TUNE_NO_PP);
+    // Cost model in units of "one k-tile of a 256x256 block" (calibrated with tools/gemm_bench.py, same-box A/B):
+    // a block owns its CU, so a launch costs rounds x (k-tiles x tk + fixed), fixed = prologue + exposed epilogue.
+    int cfg = -1, cfg_ok = -1;
+    double best = 1e30, best_fill = 0.0, best_ok = 1e30, fill_ok = 0.0;
+    for (int ci = 0; ci < NUM_BIG_TILES && base_ok; ++ci) {
+        const BigTile& c = BIG_TILES[ci];
+        if (forced >= 0 && ci != forced) continue;
+        // (the 192-row ping-pong tile serves the dense M = 8192-class layers; as a conv tile it measured 7 % behind the 256 x 320 one on
+        //  8192 x 1280 x 11520 / 17280 - more operand bytes per flop - and is taken for convs only when forced)
+        if (ci == PP192_TILE && conv && forced != ci) continue;
+        if ((ci == PP_TILE || ci == PP320_TILE || ci == PP192_TILE) && !pp_ok) continue;
+        if (d->N % c.bn != 0 || (geglu && !c.geglu_ok) || ((d->flags & ICD_GEMM_TUNE_BN256) && c.bn != 256)) continue;
+        const long long b0 = (long long)((d->M + c.bm - 1) / c.bm) * (d->N / c.bn);
+        const int smax = split_allowed(d) && b0 < 192 && nk_total >= 16 ? split_depth(8, nk_total, d->M, d->N, d->splitk_ws_bytes) : 1;
+        for (int sx = 1; sx <= smax; ++sx) {
+            const long long bt = b0 * sx;
+            const long long full = bt / 256, rem = bt % 256;
+            // rounds are strict for the first two (all blocks in lockstep), later ones desynchronise
+            const double rounds = bt <= 512 ? (double)((bt + 255) / 256) : (double)full + (rem ? 0.3 + 0.7 * rem / 256.0 : 0.0);
+            const double act = bt >= 256 ? 256.0 : (double)bt;
+            const double w = act <= 160 ? 0.0 : act >= 200 ? 1.0 : (act - 160) / 40.0;
+            const double tk = c.tk_part + w * (c.tk_full - c.tk_part);
+            const int kps = (nk_total + sx - 1) / sx;
+            double cost = rounds * (kps * tk + c.fixed);
+            if (sx > 1) cost += (double)(sx + 1) * d->M * d->N * 4.0 / 3.5e12 / 1.5e-6 + 4.0;   // fp32 partials + reduce launch
+            // (round 6: the cheapest candidate is picked as before and the launch goes to the 128-wide kernels when it fills its last round
+            //  below 45 % - UNLESS an un-split candidate fills well: 2048 x 2560 x 1280 lost its 128 x 320 tile (128 blocks) to the 128 x 128
+            //  kernel the day a cheaper-looking 192 x 256 entry (110 blocks) appeared.  Split-K candidates are not rescued this way: 2048 x 1280
+            //  x 1280 on 128 x 320 split 2 measured 26.2 us against 17.9 on the 128 x 128 kernel.)
+            const double fill = (double)bt / (double)(((bt + 255) / 256) * 256);
+            if (fill >= 0.45 && sx == 1 && cost < best_ok) { best_ok = cost; cfg_ok = ci; fill_ok = fill; }
+            if (cost < best) { best = cost; cfg = ci; *split = sx; best_fill = fill; }
+        }
+    }
+    if (cfg >= 0 && best_fill < 0.45 && !force && cfg_ok >= 0) { cfg = cfg_ok; *split = 1; best_fill = fill_ok; }
+    return cfg >= 0 && (best_fill >= 0.45 || force) ? cfg : -1;
+}
+
+// Host tile of the fused query projection + cross-attention launch.
+static void plan_xattn(const icd_gemm_desc* d, GemmPlan* p) {
+    const int tune = d->tune_xattn_tile;
+    // 128 x 128 tiles with two resident blocks per CU (measured, SDXL 32x32 level: 63.8 us at B = 8 / 98.9 us at B = 16 against
+    // 73.8 / 113.1 us with 256 x 128 tiles, whose partial last round costs a whole tile; the two launches it replaces take
+    // 67.3 / 109.9 us); the 256-row tile stays available for tuning
+    // ... and since the 256 x 256 tile of gemm_big.hip hosts it (a block = 256 queries x 4 heads, K / V^T staged once in the
+    // idle operand stages): the fast GEMM tile under the same epilogue, LayerNorm statistics from its own main loop
+    if ((tune == 0 || tune == 5 || tune == 6) && d->N % 256 == 0 && (long long)(d->M / 256) * (d->N / 256) >= 32) {
+        // 256 or 192 query rows per block: the 192-row tile lays ceil(rps / 192) m-tiles over every sample (the last one partial), which
+        // turns the 160 blocks of SDXL's 1024-token layers at 8 images per GPU into 240 - one round on 256 CUs either way, of blocks
+        // with 3/4 of the work.  Whichever needs less (rounds x rows per block); tune_xattn_tile 5 / 6 force 256 / 192 (A/B)
+        const long long nb = d->N / 256, b256 = (long long)(d->M / 256) * nb;
+        const int bps192 = (d->rows_per_sample + 191) / 192;
+        const long long b192 = (long long)(d->M / d->rows_per_sample) * bps192 * nb;
+        const long long t256 = (b256 + 255) / 256 * 256, t192 = (b192 + 255) / 256 * 192;
+        const bool t192_wins = tune == 6 || (tune == 0 && t192 < t256);
+        p->family = Tile::Big; p->cfg = t192_wins ? XATTN_TILE_192 : XATTN_TILE_256; p->tile_m = t192_wins ? 192 : 256; p->tile_n = 256;
+        p->nbm = t192_wins ? (d->M / d->rows_per_sample) * bps192 : d->M / 256; p->nbn = d->N / 256;
+        p->ln_inline = (d->flags & ICD_GEMM_LN_COMPUTE) && p->nbn <= 12 && !(d->flags & ICD_GEMM_TUNE_NO_LN_INLINE);
+        return;
+    }
+    p->family = Tile::XattnHost; p->wm = tune == 4 ? 4 : 2; p->tile_m = p->wm * 64; p->tile_n = 128;
+    p->nbm = d->M / p->tile_m; p->nbn = d->N / 128;
+}
+
+static int gemm_plan(const icd_gemm_desc* d, GemmPlan* p) {
+    const bool trans = d->flags & ICD_GEMM_OUT_TRANS, ln_compute = d->flags & ICD_GEMM_LN_COMPUTE, conv = d->mode == 1;
+    const int nk_total = (d->K + BK - 1) / BK;
+    int s = 1;          // split depth asked for; set_split turns it into (k-tiles per split, splits)
+    *p = GemmPlan{}; p->gm = d->tune_group_m > 0 ? d->tune_group_m : 1; p->kt_per_split = nk_total; p->batch = d->batch > 0 ? d->batch : 1;
+    if (d->xattn_k) {
+        plan_xattn(d, p);
+    } else if ((p->cfg = pick_big_tile(d, &s)) >= 0) {
+        const BigTile& c = BIG_TILES[p->cfg];
+        p->family = Tile::Big; p->tile_m = c.bm; p->tile_n = c.bn; p->nbm = (d->M + c.bm - 1) / c.bm; p->nbn = d->N / c.bn;
+        set_split(p, nk_total, s);
+        // every n-tile recomputes the statistics of its rows (a few % of its main loop): free up to ~10 n-tiles (to_q / to_qk:
+        // 65.1 vs 65.7 us at 8192 x 2560 x 1280), dearer than the 8 us statistics launch on the 40 n-tiles of a GEGLU
+        // projection (243.9 vs 229.5 + 8)
+        p->ln_inline = ln_compute && !conv && p->ksplit == 1 && !trans && !(d->flags & (ICD_GEMM_OUT_F32 | ICD_GEMM_RESID_F32)) &&
+                       !(d->flags & ICD_GEMM_TUNE_NO_LN_INLINE) && p->nbn <= 12 && !d->out_carry && !d->resid_carry;
+    } else {
+        plan_gemm(d->M, d->N, d->K, p->batch, split_allowed(d), d->splitk_ws_bytes, &p->wm, &s);
+        if (d->flags & ICD_GEMM_TUNE_WM2) { p->wm = 2; s = 1; }          // tuning overrides (tools/gemm_bench.py)
+        if (d->flags & ICD_GEMM_TUNE_WM4) { p->wm = 4; s = 1; }
+        set_split(p, nk_total, s);
+        if (conv) {
+            ICD_CHECK_ARG(p->batch == 1 && !trans, "icd_gemm: conv mode is not batched / transposed");      // (the big tiles store V^T from a conv)
+            p->family = conv_aligned(d) ? Tile::ConvFast : Tile::ConvGeneral;
+            if (p->family == Tile::ConvGeneral) p->wm = 2;          // the general loader has one height
+        }
+        p->tile_m = p->wm * 64; p->nbm = (d->M + p->tile_m - 1) / p->tile_m; p->nbn = (d->N + BN - 1) / BN;
+    }
+    if (p->cfg < NUM_BIG_TILES) p->gm = group_m(d, p->nbn);          // (the fused cross-attention big tiles keep the caller's)
+    // ICD_GEMM_LN_COMPUTE: the big tiles compute the statistics in their main loop; every other path runs the statistics launch
+    p->ln_stats_pass = ln_compute && !p->ln_inline;
+    ICD_CHECK_ARG(!p->ln_stats_pass || d->lda == d->K, "icd_gemm: ICD_GEMM_LN_COMPUTE on this path needs contiguous rows (lda == K)");
+    return ICD_OK;
+}
+
+// descriptor + plan -> the kernels' argument struct
+static void gemm_args(const icd_gemm_desc* d, const GemmPlan& p, GemmK& k) {
+    k.a0 = (const half_t*)d->a0; k.a1 = (const half_t*)d->a1; k.w = (const half_t*)d->w;
+    k.bias = d->bias; k.rowbias = (const half_t*)d->rowbias; k.resid = (const half_t*)d->resid; k.out = d->out; k.partial = (float*)d->splitk_ws;
+    k.M = d->M; k.N = d->N; k.K = d->K; k.Nw = d->Nw > 0 ? d->Nw : d->N;
+    k.lda = d->lda; k.ldw = d->ldw; k.ldo = d->ldo; k.ldr = d->ldr; k.ld_rowbias = d->ld_rowbias;
+    k.rps = d->rows_per_sample > 0 ? d->rows_per_sample : 1;
+    k.C0 = d->C0; k.C1 = d->C1; k.Hin = d->Hin; k.Win = d->Win; k.Hout = d->Hout; k.Wout = d->Wout;
+    k.ksize = d->ksize; k.stride = d->stride; k.upsample = d->upsample;
+    if (d->mode == 0) { k.ksize = 0; k.Hout = 0; }          // launch_big / launch_pp tell a conv by these; every dense launch now (MODE 0 kernels never read them)
+    k.tapmap = 0x876543210ULL | ((unsigned long long)conv_taps(d) << 60);
+    if (d->conv_ktaps) {          // phase form: taps {t0, t0 + 1, t0 + 3, t0 + 4}
+        const unsigned long long t0 = (unsigned long long)d->conv_tap_base;
+        k.tapmap = t0 | ((t0 + 1) << 4) | ((t0 + 3) << 8) | ((t0 + 4) << 12) | (4ULL << 60);
+    }
+    const unsigned W = (unsigned)d->out_remap_w;          // row map of the phase form, or the identity
+    k.orm_pack = W ? 2u | ((2u * W) << 2) | ((unsigned)d->out_remap_c << 17) : 1u; k.orm_magic = W ? orm_magic_of(W) : 0u;
+    k.zdiv = d->zdiv > 0 ? d->zdiv : 1; k.a_bs0 = d->a_bs0; k.a_bs1 = d->a_bs1; k.w_bs0 = d->w_bs0; k.w_bs1 = d->w_bs1; k.o_bs0 = d->o_bs0; k.o_bs1 = d->o_bs1;
+    k.alpha = d->alpha; k.flags = d->flags;
+    k.timeline = (unsigned long long*)d->debug_timeline; k.out32 = d->out_f32;
+    k.resid_c = (const unsigned char*)d->resid_carry; k.out_c = (unsigned char*)d->out_carry;
+    k.ln_stats = d->ln_stats; k.ln_s = d->ln_colsum; k.ln_eps = d->ln_eps > 0.f ? d->ln_eps : 1e-5f;
+    k.ln_stats_w = p.ln_inline ? const_cast<float*>(d->ln_stats) : nullptr;
+    k.xk = (const half_t*)d->xattn_k; k.xvt = (const half_t*)d->xattn_vt;
+    k.x_nk = d->xattn_nk; k.x_ldk = d->xattn_ldk; k.x_ldvt = d->xattn_ldvt; k.x_vt_bs = d->xattn_vt_bs;
+    k.x_scale_log2 = d->xattn_scale * ATTN_LOG2E;
+    k.nbm = p.nbm; k.nbn = p.nbn; k.gm = p.gm; k.ksplit = p.ksplit; k.kt_per_split = p.kt_per_split;
+}
+
+static int gemm_launch(const GemmK& k, const GemmPlan& p, hipStream_t st) {
+    int rc = p.ln_stats_pass ? icd_layernorm_stats(k.a0, k.M, k.K, k.ln_eps, const_cast<float*>(k.ln_stats), st) : ICD_OK;
+    if (rc != ICD_OK) return rc;
+    const bool tall = p.wm == 4;
+    switch (p.family) {
+    case Tile::Big: rc = launch_big(k, p.cfg, st); break;
+    case Tile::XattnHost: rc = tall ? launch<0, false, 4, 3, true>(k, 1, st) : launch<0, false, 2, 2, true>(k, 1, st); break;
+    case Tile::ConvGeneral: rc = launch<2, false, 2, 2>(k, 1, st); break;
+    case Tile::ConvFast: rc = tall ? launch<1, false, 4, 3>(k, 1, st) : launch<1, false, 2, 2>(k, 1, st); break;
+    case Tile::Dense128:
+        rc = k.flags & ICD_GEMM_OUT_TRANS ? (tall ? launch<0, true, 4, 3>(k, p.batch, st) : launch<0, true, 2, 2>(k, p.batch, st))
+                                          : (tall ? launch<0, false, 4, 3>(k, p.batch, st) : launch<0, false, 2, 2>(k, p.batch, st));
+    }
+    return rc == ICD_OK && k.ksplit > 1 ? launch_reduce(k, st) : rc;
+}
+
+static int gemm_decide(const icd_gemm_desc* d, GemmPlan* p) { const int rc = gemm_validate(d); return rc == ICD_OK ? gemm_plan(d, p) : rc; }
+
+extern "C" int icd_gemm(const icd_gemm_desc* d, void* stream) {
+    GemmPlan p; GemmK k;
+    const int rc = gemm_decide(d, &p);
+    if (rc != ICD_OK) return rc;
+    gemm_args(d, p, k);
+    return gemm_launch(k, p, (hipStream_t)stream);
+}
 
 extern "C" int icd_gemm_plan(const icd_gemm_desc* d, icd_gemm_plan_info* out) {
     ICD_CHECK_ARG(out != nullptr, "icd_gemm_plan: null output");
     memset(out, 0, sizeof(*out));
-    return gemm_run(d, nullptr, out, false);
+    GemmPlan p;
+    const int rc = gemm_decide(d, &p);
+    if (rc == ICD_OK) *out = {p.family == Tile::Big, p.tile_m, p.tile_n, p.ksplit, p.ln_inline, d->xattn_k != nullptr, p.cfg, p.gm};
+    return rc;
 }

@@ -504,9 +504,9 @@ int launch_big(const GemmK& k, int cfg, hipStream_t st) {
     case PP192_TILE: return launch_pp(k, st, 192); // 192 x 256 with it
     }
 #undef ICD_BIG
-    if (cfg == 100)   // query projection + cross-attention in one launch (icd_gemm_desc.xattn_*): 256 x 256 = 256 queries x 4 heads
+    if (cfg == XATTN_TILE_256)   // query projection + cross-attention in one launch (icd_gemm_desc.xattn_*): 256 x 256 = 256 queries x 4 heads
         return k.x_nk <= 80 ? launch_one<0, 2, 4, 4, 2, true, true, true>(k, st) : launch_one<0, 2, 4, 4, 2, true, false, true>(k, st);   // 5 / 6 live key slots
-    if (cfg == 101)   // the same on 192 x 256: six m-tiles per 1024-query sample (the last one 64 rows) - 240 blocks where 160 leave 96 CUs idle
+    if (cfg == XATTN_TILE_192)   // the same on 192 x 256: six m-tiles per 1024-query sample (the last one 64 rows) - 240 blocks where 160 leave 96 CUs idle
         return k.x_nk <= 80 ? launch_one<0, 2, 4, 3, 2, true, true, true>(k, st) : launch_one<0, 2, 4, 3, 2, true, false, true>(k, st);
     icd_set_error("icd_gemm: unknown big-tile configuration %d", cfg);
     return ICD_ERR_INVALID_ARG;

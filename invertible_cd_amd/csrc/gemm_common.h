@@ -206,6 +206,8 @@ constexpr int NUM_BIG_TILES = 7;
 constexpr int PP_TILE = 4;                       // index of the ping-pong 256 x 256 tile (gemm_pp.hip)
 constexpr int PP320_TILE = 5;                    //              ... 256 x 320 tile (gemm_pp320.hip)
 constexpr int PP192_TILE = 6;                    //              ... 192 x 256 tile (gemm_pp.hip, TM = 3)
+constexpr int XATTN_TILE_256 = 100;              // launch_big's cfg of the fused cross-attention launch on 256 x 256 (no BIG_TILES row: never costed)
+constexpr int XATTN_TILE_192 = 101;              //              ... on 192 x 256
 constexpr BigTile BIG_TILES[NUM_BIG_TILES] = {
     {256, 256, true, 1.00, 1.08, 9.5},
     {256, 320, false, 1.07, 1.30, 13.5},
