@@ -166,6 +166,34 @@ int icd_gemm_plan(const icd_gemm_desc* d, icd_gemm_plan_info* out);
 /* Bytes of split-K scratch icd_gemm would like for this shape (0: the shape is not split). */
 int64_t icd_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K);
 
+/* The GEGLU feed-forward of a BasicTransformerBlock in ONE launch (ffn_fused.hip):
+ *     out = resid + (value * gelu(gate)) W2^T + b2,      [value | gate] = LN(x) W1^T + b1
+ * i.e. icd_gemm with ICD_GEMM_GEGLU followed by the output projection, with the same operands: w1 fp16 [2 hidden, ldw1] and b1 /
+ * ln_colsum fp32 [2 hidden] interleaved in 32-column groups as ICD_GEMM_GEGLU takes them (gamma folded, see icd_gemm_desc.ln_stats),
+ * w2 fp16 [C, ldw2].  The hidden tensor is rounded to fp16 as the two launches round it, but never reaches memory.  Built for
+ * C = 320, hidden = 1280; any other width is ICD_ERR_INVALID_ARG (nothing is enqueued).  flags: ICD_GEMM_LN_COMPUTE (ln_stats is an
+ * OUTPUT: the statistics are taken from x in the launch, eps = ln_eps) and ICD_GEMM_RESID_F32.  ln_stats / ln_colsum both NULL: no
+ * LayerNorm; one without the other is ICD_ERR_INVALID_ARG.  resid may alias out (same rows: an in-place add).  out_f32, resid_carry, out_carry: as in icd_gemm_desc. */
+typedef struct {
+    const void* x;            /* fp16 [M, ldx] */
+    const void* w1;
+    const float* b1;          /* or NULL */
+    const void* w2;
+    const float* b2;          /* fp32 [C] or NULL */
+    const void* resid;        /* fp16 (fp32 with ICD_GEMM_RESID_F32) [M, ldr] or NULL */
+    void* out;                /* fp16 [M, ldo] */
+    int32_t M, C, hidden;
+    int32_t ldx, ldw1, ldw2, ldo, ldr;
+    int32_t flags;
+    float ln_eps;             /* 0 -> 1e-5 */
+    const float* ln_stats;
+    const float* ln_colsum;
+    float* out_f32;
+    const void* resid_carry;
+    void* out_carry;
+} icd_ffn_desc;
+int icd_ffn_geglu(const icd_ffn_desc* d, void* stream);
+
 /* GroupNorm(32 groups, affine, eps) [+ SiLU] over NHWC fp16, input optionally the channel concat of two tensors
  * (up-block skip connections), output a single NHWC tensor.  stats_ws: >= B*split*groups*2 floats.
  * Replaces: torch group_norm + silu in ResnetBlock2D / Transformer2DModel.norm / conv_norm_out. */
@@ -486,6 +514,13 @@ int32_t icd_unet_num_attention_layers(const icd_unet* u);
  * A/B of a tile family over a whole forward (bench.py --gemm-tune); 0 (default) = the planner's own choice.  Results differ by fp32 summation
  * order where a different split-K plan is taken, not otherwise. */
 #define ICD_UNET_OPT_GEMM_TUNE       8
+/* ICD_UNET_OPT_FFN_FUSION: the GEGLU projection and the output projection of a BasicTransformerBlock's feed-forward as ONE launch
+ * (icd_ffn_geglu; the 4C-wide hidden tensor is neither allocated nor written): 0 never, 1 wherever the kernel exists (C = 320),
+ * 2 (default): C = 320 with at least 65536 tokens in the batch and no ICD_UNET_OPT_GEMM_TUNE A/B of the GEMM tiles in force.  The fused
+ * launch measured faster at 131072 tokens (four rounds of 128-row workgroups on 256 CUs) and at 32768; the 32768-token batch keeps the two
+ * launches all the same, because a test pins their planner records at B = 8, and 65536 (two rounds, not measured) is inferred from the
+ * measurements on either side.  Results differ by fp32 summation order. */
+#define ICD_UNET_OPT_FFN_FUSION      9
 #define ICD_SPLIT_GN          1    /* every GroupNorm normalises fp16 + carry (skip tensors keep their carry for it) */
 #define ICD_SPLIT_CONV1       2    /* conv1 of a ResnetBlock2D hands its output to GroupNorm 2 with a carry */
 #define ICD_SPLIT_SHORTCUT    4    /* conv_shortcut over [x | lo] (needs ICD_SPLIT_GN: that GroupNorm writes lo) */

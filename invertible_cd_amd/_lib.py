@@ -24,6 +24,7 @@ ICD_UNET_OPT_RESIDUAL_F32 = 5           # round-3 name
 ICD_UNET_OPT_SPLIT_MASK = 6
 ICD_UNET_OPT_UPSAMPLE_PHASES = 7
 ICD_UNET_OPT_GEMM_TUNE = 8
+ICD_UNET_OPT_FFN_FUSION = 9
 ICD_GEMM_TUNE_NO_PP = 0x20000000
 ICD_SPLIT_GN, ICD_SPLIT_CONV1, ICD_SPLIT_SHORTCUT, ICD_SPLIT_PROJ_OUT, ICD_SPLIT_DOWN, ICD_SPLIT_SAMPLER_OUT, ICD_SPLIT_UP, ICD_SPLIT_TEMB = 1, 2, 4, 8, 16, 32, 64, 128
 ICD_SPLIT_QK = 256
@@ -58,6 +59,15 @@ class GemmDesc(C.Structure):
         ("resid_carry", C.c_void_p), ("out_carry", C.c_void_p),
         ("conv_tap_base", C.c_int32), ("conv_ktaps", C.c_int32), ("out_remap_w", C.c_int32), ("out_remap_c", C.c_int32),
     ]
+
+
+class FfnDesc(C.Structure):
+    """icd_ffn_desc: the GEGLU feed-forward in one launch (icd_ffn_geglu)."""
+    _fields_ = [("x", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("resid", C.c_void_p),
+                ("out", C.c_void_p), ("M", C.c_int32), ("C", C.c_int32), ("hidden", C.c_int32), ("ldx", C.c_int32), ("ldw1", C.c_int32),
+                ("ldw2", C.c_int32), ("ldo", C.c_int32), ("ldr", C.c_int32), ("flags", C.c_int32), ("ln_eps", C.c_float),
+                ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p), ("out_f32", C.c_void_p), ("resid_carry", C.c_void_p),
+                ("out_carry", C.c_void_p)]
 
 
 class ProbsEpilogue(C.Structure):
@@ -115,6 +125,7 @@ SIGNATURES = {
     "icd_build_sha": (C.c_char_p, []),
     "icd_gemm": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p]),
     "icd_gemm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "icd_ffn_geglu": (C.c_int, [C.POINTER(FfnDesc), C.c_void_p]),
     "icd_groupnorm": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icd_groupnorm_ws_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -286,7 +286,7 @@ class UNet2DConditionModel:
                "xattn_tile": _lib.ICD_UNET_OPT_XATTN_TILE, "attn_valu_scale": _lib.ICD_UNET_OPT_ATTN_VALU_SCALE,
                "residual": _lib.ICD_UNET_OPT_RESIDUAL_MODE, "residual_f32": _lib.ICD_UNET_OPT_RESIDUAL_MODE,
                "split_mask": _lib.ICD_UNET_OPT_SPLIT_MASK, "upsample_phases": _lib.ICD_UNET_OPT_UPSAMPLE_PHASES,
-               "gemm_tune": _lib.ICD_UNET_OPT_GEMM_TUNE}
+               "gemm_tune": _lib.ICD_UNET_OPT_GEMM_TUNE, "ffn_fusion": _lib.ICD_UNET_OPT_FFN_FUSION}
 
     # ------------------------------------------------------------------ precision policy
     # Numerical precision of the residual stream and of its consumers (icd_unet options residual / split_mask):
@@ -371,6 +371,7 @@ class UNet2DConditionModel:
 
     def set_option(self, name, value):
         """Per-handle execution option (icd_unet_set_option): 'xattn_fusion' 0 / 1 / 2, 'ln_inline_stats' 0 / 1, 'xattn_tile' 0 / 2 / 4 / 5 / 6,
+        'ffn_fusion' 0 / 1 / 2 (the GEGLU feed-forward as one launch: never / wherever the kernel exists / from 65536 tokens on),
         'residual' 0 fp16 stream / 1 fp32 twin / 2 error carry / 3 carry + split consumers (default; 'residual_f32' is the round-3
         name of the same option).  A/B
         tuning and tests; nothing is process-wide."""
@@ -384,6 +385,9 @@ class UNet2DConditionModel:
             self._kv = None
             self._ws_pool.clear()
             self._ws_key = None                  # the arena holds the twins / carries of the residual stream: size it again
+        if name in ("ffn_fusion", "gemm_tune"):
+            self._ws_pool.clear()
+            self._ws_key = None                  # the fused feed-forward allocates no hidden tensor: the arena's peak moves
         return self
 
     # ------------------------------------------------------------------ duck-typed nn.Module surface

@@ -5,6 +5,7 @@
     python tools/gemm_bench.py dense 131072 320 320          # M N K
     python tools/gemm_bench.py geglu 131072 2560 320
     python tools/gemm_bench.py attn 32 8 4096 4096 40        # B H Nq Nk d
+    python tools/gemm_bench.py ffn 131072                    # M: icd_ffn_geglu (C = 320) against the GEGLU + output-projection pair
 """
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +18,53 @@ iters = int(os.environ.get("ITERS", "20"))
 dev = "cuda"
 g = torch.Generator(device=dev).manual_seed(0)
 rnd = lambda *s: torch.randn(*s, device=dev, generator=g).half()
+if kind == "ffn":
+    # the executor's feed-forward on the SAME buffers (in place, LayerNorm statistics in the launch, error carry): one fused launch against
+    # the two it replaces, visited round-robin ROUNDS times; min, median and the spread (max - min) / min of each over the rounds
+    import ctypes as C
+    from invertible_cd_amd import _lib
+    M, Cc = a[0], 320
+    lib, st_ = _lib.load(), lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    x, xc = rnd(M, Cc), torch.zeros(M, Cc, device=dev, dtype=torch.uint8)
+    w1, w2 = rnd(8 * Cc, Cc) * Cc ** -0.5, rnd(Cc, 4 * Cc) * (4 * Cc) ** -0.5
+    b1, b2, cs = torch.zeros(8 * Cc, device=dev), torch.zeros(Cc, device=dev), w1.float().sum(1)
+    lnst, hid = torch.zeros(M, 2, device=dev), torch.empty(M, 4 * Cc, device=dev, dtype=torch.float16)
+    x0 = x.clone()
+    def fused():
+        d = _lib.FfnDesc()
+        d.x, d.w1, d.b1, d.w2, d.b2, d.resid, d.out = x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), x.data_ptr(), x.data_ptr()
+        d.M, d.C, d.hidden, d.ldx, d.ldw1, d.ldw2, d.ldo, d.ldr = M, Cc, 4 * Cc, Cc, Cc, 4 * Cc, Cc, Cc
+        d.flags, d.ln_stats, d.ln_colsum, d.resid_carry, d.out_carry = _lib.ICD_GEMM_LN_COMPUTE, lnst.data_ptr(), cs.data_ptr(), xc.data_ptr(), xc.data_ptr()
+        _lib.check(lib.icd_ffn_geglu(C.byref(d), st_()))
+    def pair():
+        d = _lib.GemmDesc()
+        d.a0, d.w, d.bias, d.out = x.data_ptr(), w1.data_ptr(), b1.data_ptr(), hid.data_ptr()
+        d.M, d.N, d.K, d.Nw, d.lda, d.ldw, d.ldo = M, 8 * Cc, Cc, 8 * Cc, Cc, Cc, 4 * Cc
+        d.mode, d.batch, d.zdiv, d.alpha, d.flags = 0, 1, 1, 1.0, _lib.ICD_GEMM_GEGLU | _lib.ICD_GEMM_LN_COMPUTE
+        d.ln_stats, d.ln_colsum = lnst.data_ptr(), cs.data_ptr()
+        _lib.check(lib.icd_gemm(C.byref(d), st_()))
+        e = _lib.GemmDesc()
+        e.a0, e.w, e.bias, e.resid, e.out = hid.data_ptr(), w2.data_ptr(), b2.data_ptr(), x.data_ptr(), x.data_ptr()
+        e.M, e.N, e.K, e.Nw, e.lda, e.ldw, e.ldo, e.ldr = M, Cc, 4 * Cc, Cc, 4 * Cc, 4 * Cc, Cc, Cc
+        e.mode, e.batch, e.zdiv, e.alpha, e.resid_carry, e.out_carry = 0, 1, 1, 1.0, xc.data_ptr(), xc.data_ptr()
+        _lib.check(lib.icd_gemm(C.byref(e), st_()))
+    rounds, t = int(os.environ.get("ROUNDS", "5")), {"fused": [], "pair": []}
+    for r in range(rounds + 1):                  # (round 0 warms up and is dropped)
+        for name, f in (("pair", pair), ("fused", fused)):
+            x.copy_(x0); xc.zero_()              # the stream is updated in place: every timing starts from the same values
+            f(); torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            if r:
+                t[name].append(e0.elapsed_time(e1) / iters * 1e3)
+    for name in ("pair", "fused"):
+        v = sorted(t[name])
+        print(f"ffn M={M} C={Cc} {name}: {v[0]:.1f} us (min of {rounds}; median {v[len(v) // 2]:.1f}, spread {100 * (v[-1] - v[0]) / v[0]:.1f} %)")
+    print(f"ffn M={M}: fused / pair = {min(t['fused']) / min(t['pair']):.3f} (min), {sorted(t['fused'])[rounds // 2] / sorted(t['pair'])[rounds // 2]:.3f} (median)")
+    sys.exit(0)
 if kind == "conv":
     B, H, W, Ci, Co = a
     x, w, b = rnd(B * H * W, Ci), rnd(Co, 9 * Ci) * (9 * Ci) ** -0.5, torch.zeros(Co, device=dev)

@@ -33,6 +33,8 @@ def family(k):
     m = re.search(r"gemm(?:_big|_pp320|_pp)?_kernel<(\d)", k)
     if m:
         return "gemm_dense" if m.group(1) == "0" else "gemm_conv"
+    if "ffn_fused" in k:                     # the fused feed-forward is profiled as gemm_dense (runtime.hip), one launch for two
+        return "gemm_dense"
     for pat, f in (("splitk_reduce", "splitk_reduce"), ("attn_probs", "softmax"), ("attn_fused", "attn_fused"), ("attn_cross", "attn_fused"),
                    ("gn_", "groupnorm"), ("layernorm", "layernorm"), ("softmax", "softmax")):
         if pat in k:

@@ -19,7 +19,7 @@ for arch in ${ARCHS:-sd15 sdxl}; do
   python tools/rocpd_stats.py "$db" > $OUT/${TAG}_bench_${arch}_b${b}_kernel_stats.txt 2>> $OUT/rocprof_$arch.err
   # (counters on this library's kernels only - torch's weight-building kernels run unserialised - and every pass under a timeout: an
   #  unrestricted SDXL pass once sat for an hour)
-  KR='--kernel-include-regex gemm|attn|gn_|splitk|layernorm|conv_out|carry|split2|pack|sinusoid|x0_step|activation'
+  KR='--kernel-include-regex gemm|ffn_fused|attn|gn_|splitk|layernorm|conv_out|carry|split2|pack|sinusoid|x0_step|activation'
   timeout -k 5 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv $KR -d $OUT/pmcF_$arch -o p -- python bench.py --full --arch $arch --steps 1 --warmup 1 --in-flight 1 --no-cpu-baseline --no-vae --no-ref-batching --no-profile --no-sdxl --no-edit > /dev/null 2> $OUT/pmcF_$arch.err
   timeout -k 5 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv $KR -d $OUT/pmcW_$arch -o p -- python bench.py --full --arch $arch --steps 1 --warmup 1 --in-flight 1 --no-cpu-baseline --no-vae --no-ref-batching --no-profile --no-sdxl --no-edit > /dev/null 2> $OUT/pmcW_$arch.err
   python tools/hbm_traffic.py $OUT/pmcF_$arch $OUT/pmcW_$arch --arch $arch --batch $b > $OUT/${TAG}_hbm_traffic_${arch}_b${b}.json 2>> $OUT/pmcF_$arch.err

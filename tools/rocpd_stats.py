@@ -40,6 +40,8 @@ def main(path):
             f = "xattn_fused"
         elif m:
             f = "gemm_dense" if m.group(1) == "0" else "gemm_conv"
+        elif "ffn_fused" in n:                   # booked under gemm_dense by the executor's profiler
+            f = "gemm_dense"
         elif "attn_probs" in n:
             f = "softmax (one-pass probabilities)"
         elif "splitk_reduce" in n:
@@ -62,7 +64,7 @@ def main(path):
 
     # idle time between consecutive kernels of the product library (start[i+1] - end[i], overlaps count as 0), restricted to the
     # steady region: pairs whose gap is < 50 us (longer gaps are host-side pauses between steps / phases of the script)
-    ours = sorted((s_, e_, short(n)) for n, s_, e_ in rows if re.search(r"gemm|attn|gn_|layernorm|conv_out|x0_step|sinusoid|silu|geglu|softmax|upsample|embed", n))
+    ours = sorted((s_, e_, short(n)) for n, s_, e_ in rows if re.search(r"gemm|ffn_fused|attn|gn_|layernorm|conv_out|x0_step|sinusoid|silu|geglu|softmax|upsample|embed", n))
     gaps, busy = [], 0
     for (s0, e0, _), (s1, e1, _) in zip(ours, ours[1:]):
         g = s1 - e0
