@@ -393,7 +393,7 @@ int icd_p2p_cross_edit_groups(void* probs, int32_t n_groups, int32_t n_prompts, 
  * out[p] = x[0] + float(mask_p) * (x[p] - x[0]).  maps[l]: fp16 [n_prompts * heads[l], res*res, ld] (the accumulated
  * AttentionStore tensors, row stride ld >= n_words), alpha / alpha_sub: fp32 [n_prompts][n_words] word masks, x: [n_prompts, C,
  * H, W] fp16 or fp32, out: fp32 (torch's promotion of `base + mask.float() * (x_t - base)`).  maps / heads are HOST arrays of
- * n_layers <= 8 entries. */
+ * n_layers <= 64 entries (SD1.5 at 64 x 64 latents: 5 layers at res 16; SDXL at 128 x 128: 50 layers of 20 heads at res 32). */
 int icd_local_blend(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_prompts, int32_t res,
                     int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, float th_pool, float th_sub,
                     const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W, float* out, void* stream);
@@ -407,9 +407,24 @@ int icd_local_blend_groups(const void* const* maps, const int32_t* heads, int32_
                            int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
                            const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
                            float* out, void* stream);
+/* The same with a workspace of icd_local_blend_workspace_bytes(n_groups, n_prompts, res) bytes of device memory: a reduce launch writes
+ * every prompt's word-weighted head-and-layer mean (fp32 [n_groups * n_prompts][main | substruct words][res * res]) there once, and the
+ * pool / threshold / blend launch reads it, where the entries above have every block rebuild its base prompt's maps.  The terms are added
+ * in the same order either way (words, then heads, then layers), so the result is the same bit for bit; workspace == NULL is
+ * icd_local_blend_groups.  The workspace is free again when the work queued on `stream` has run. */
+int64_t icd_local_blend_workspace_bytes(int32_t n_groups, int32_t n_prompts, int32_t res);
+int icd_local_blend_groups_ws(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
+                              int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
+                              const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
+                              float* out, void* workspace, int64_t workspace_bytes, void* stream);
 /* dst[t][i] += src[t][i] (fp16, rounded like torch's in-place add) for up to 32 tensors in one launch: the per-step accumulation
  * of AttentionStore.between_steps (utils/p2p.py:164-170).  dst / src / counts are HOST arrays; tensors 16-byte aligned. */
 int icd_accumulate_multi(void* const* dst, const void* const* src, const int64_t* counts, int32_t n_tensors, void* stream);
+/* The same for any number of tensors (1 .. 65535) in one launch - an SDXL step stores 130 maps -, the pointers in DEVICE memory:
+ * table = int64 [3][n_tensors], row 0 the dst pointers, row 1 the src pointers, row 2 the element counts, written before this call in
+ * stream order and left alone until the launch has run; max_count = the largest count (it sizes the grid).  Every tensor 16-byte
+ * aligned: the caller checks it, the table is not read on the host. */
+int icd_accumulate_multi_n(const int64_t* table, int32_t n_tensors, int64_t max_count, void* stream);
 
 /* Consistency boundary step, eps-prediction (utils/generation.py:136-155 == utils/generation_sdxl.py:112-132):
  *   x0 = (x - sigma_t*eps)/alpha_t ; out = alpha_s*x0 + sigma_s*eps, (alpha_s, sigma_s) := (1, 0) where s == 0.

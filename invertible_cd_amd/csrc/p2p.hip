@@ -71,9 +71,16 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_kernel(half_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// LocalBlend (utils/p2p.py:18-44) in one launch.  Block p = prompt p; it rebuilds the base prompt's masks next to its own (the maps
-// are a few hundred KB), so no block waits for another:
+// LocalBlend (utils/p2p.py:18-44).  The heat of a prompt,
 //   heat_q[pix] = mean over (layer, head) of sum_w maps[l][(q*H_l + h), pix, w] * alpha[q][w]          (fp32)
+// is summed in ONE order everywhere: words ascending inside a (layer, head), then (layer, head) ascending - the order of the
+// one-launch kernel this file started with, so results do not depend on how the work is split.  Two ways to get it:
+//   * local_blend_heat_kernel (the reduce launch, callers that bring a workspace): every heat map is built once, [prompt][main | sub]
+//     [pix] fp32; lanes spread over (layer, head) x pixel, the (layer, head) terms of a pixel meet in LDS and one lane adds them in
+//     order.  SDXL's 50 layers x 20 heads x 1024 pixels are read once, by 64 .. 128 blocks.
+//   * in the blend kernel itself (no workspace): block p rebuilds the base prompt's heat next to its own - a few hundred KB at SD1.5's
+//     five 16 x 16 layers.
+// The blend kernel, block p = prompt p:
 //   on_q = (maxpool3x3(heat_q) / max(maxpool3x3(heat_q))) > th_pool                                      (pad = -inf, stride 1)
 //   mask_p = on_0 | on_p ;  with substruct words: mask_p &= ~(sub_0 | sub_p), sub_q = (heat'_q / max heat'_q) > th_sub, no pooling
 //   out[p] = x[0] + float(mask_p, nearest-resized to H x W) * (x[p] - x[0])     (difference in x's dtype, the rest fp32: torch's
@@ -81,12 +88,14 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_kernel(half_t* __restrict_
 // Prompt groups (batched editing): blockIdx.y = group of P contiguous prompts, every index above relative to the group's first
 // prompt, with the group's own thresholds; an inactive group (flags bit 0 clear) is copied.  Up to BLEND_MAX_GROUPS per launch.
 constexpr int BLEND_MAX_GROUPS = 32;
+constexpr int BLEND_MAX_LAYERS = 64;
 struct BlendArgs {
-    const half_t* maps[8];
-    int heads[8];
+    const half_t* maps[BLEND_MAX_LAYERS];
+    int heads[BLEND_MAX_LAYERS];
     int n_layers, P, res, n_words, ld;
     const float* alpha;          // [P][n_words]
     const float* alpha_sub;      // [P][n_words] or null
+    const float* heat;           // [P][2][res*res] from local_blend_heat_kernel, or null: the blocks build it themselves
     const void* x;               // [P][C][H][W] fp16 or fp32
     int x_f32, C, H, W;
     float* out;                  // [P][C][H][W] fp32
@@ -94,8 +103,56 @@ struct BlendArgs {
     int flags[BLEND_MAX_GROUPS]; // bit 0 active, bit 1 substruct words
 };
 
+// one (layer, head) term of one pixel: words ascending, words the mask leaves out skipped
+__device__ __forceinline__ float blend_word_sum(const half_t* __restrict__ row, const float* __restrict__ al, int n_words) {
+    float s = 0.f;
+    for (int w = 0; w < n_words; ++w) {
+        const float aw = al[w];
+        if (aw != 0.f) s += (float)row[w] * aw;
+    }
+    return s;
+}
+
+struct HeatArgs {
+    const half_t* maps[BLEND_MAX_LAYERS];
+    int heads[BLEND_MAX_LAYERS];
+    int n_layers, res2, n_words, ld, total_heads;
+    const float* alpha;          // [prompts][n_words]
+    const float* alpha_sub;      // [prompts][n_words] or null (then gridDim.z == 1)
+    float* heat;                 // [prompts][2][res2]
+};
+
+// grid (pixel tiles of HEAT_PIX, prompts, 1 | 2: main / substruct words), 256 threads = HEAT_PIX pixels x HEAT_LANES (layer, head) lanes
+constexpr int HEAT_PIX = 16, HEAT_LANES = 16, HEAT_CHUNK = 64;
+__global__ __launch_bounds__(256) void local_blend_heat_kernel(HeatArgs a) {
+    __shared__ float part[HEAT_CHUNK][HEAT_PIX + 1];
+    const int tid = threadIdx.x, px = tid & (HEAT_PIX - 1), lane = tid / HEAT_PIX;
+    const int pix = blockIdx.x * HEAT_PIX + px, q = blockIdx.y, sel = blockIdx.z;
+    const bool live = pix < a.res2;
+    const float* al = (sel ? a.alpha_sub : a.alpha) + (long long)q * a.n_words;
+    float tot = 0.f;
+    int l = 0, l_first = 0;                                            // layer of this lane's next (layer, head) term, its first term
+    for (int c0 = 0; c0 < a.total_heads; c0 += HEAT_CHUNK) {
+        const int cn = min(HEAT_CHUNK, a.total_heads - c0);
+        for (int i = lane; i < cn; i += HEAT_LANES) {
+            const int lh = c0 + i;
+            while (lh >= l_first + a.heads[l]) {                                 // lh < total_heads: l stays below n_layers
+                l_first += a.heads[l];
+                ++l;
+            }
+            const int h = lh - l_first;
+            part[i][px] = live ? blend_word_sum(a.maps[l] + (((long long)q * a.heads[l] + h) * a.res2 + pix) * a.ld, al, a.n_words) : 0.f;
+        }
+        __syncthreads();
+        if (lane == 0)
+            for (int i = 0; i < cn; ++i) tot += part[i][px];
+        __syncthreads();
+    }
+    if (lane == 0 && live) a.heat[((long long)q * 2 + sel) * a.res2 + pix] = tot / (float)a.total_heads;
+}
+
 __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
-    __shared__ float heat[1024], pooled[1024], red[256];
+    __shared__ float heat[1024], pooled[1024], red[4];
     __shared__ unsigned char mask[1024], on_tmp[1024];
     const int p = blockIdx.x, gl = blockIdx.y, tid = threadIdx.x, res2 = a.res * a.res;
     const long long per = (long long)a.C * a.H * a.W;
@@ -118,20 +175,18 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
         const int q = (pass & 1) ? p : 0;
         const bool sub = pass >= 2;
         if ((pass & 1) && p == 0) continue;                        // the base prompt's own pass is pass 0 / 2
-        const float* al = (sub ? a.alpha_sub : a.alpha) + (q0 + q) * a.n_words;
-        for (int pix = tid; pix < res2; pix += 256) {
-            float tot = 0.f;
-            for (int l = 0; l < a.n_layers; ++l)
-                for (int h = 0; h < a.heads[l]; ++h) {
-                    const half_t* row = a.maps[l] + (((q0 + q) * a.heads[l] + h) * res2 + pix) * a.ld;
-                    float s = 0.f;
-                    for (int w = 0; w < a.n_words; ++w) {
-                        const float aw = al[w];
-                        if (aw != 0.f) s += (float)row[w] * aw;
-                    }
-                    tot += s;
-                }
-            heat[pix] = tot / (float)total_heads;
+        if (a.heat) {
+            const float* hq = a.heat + ((q0 + q) * 2 + (sub ? 1 : 0)) * res2;
+            for (int pix = tid; pix < res2; pix += 256) heat[pix] = hq[pix];
+        } else {
+            const float* al = (sub ? a.alpha_sub : a.alpha) + (q0 + q) * a.n_words;
+            for (int pix = tid; pix < res2; pix += 256) {
+                float tot = 0.f;
+                for (int l = 0; l < a.n_layers; ++l)
+                    for (int h = 0; h < a.heads[l]; ++h)
+                        tot += blend_word_sum(a.maps[l] + (((q0 + q) * a.heads[l] + h) * res2 + pix) * a.ld, al, a.n_words);
+                heat[pix] = tot / (float)total_heads;
+            }
         }
         __syncthreads();
         float mx = -INFINITY;
@@ -148,13 +203,10 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
             pooled[pix] = v;
             mx = fmaxf(mx, v);
         }
-        red[tid] = mx;
+        mx = wave_max(mx);                                          // (a maximum does not depend on the order it is taken in)
+        if ((tid & 63) == 0) red[tid >> 6] = mx;
         __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
-            __syncthreads();
-        }
-        mx = red[0];
+        mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         const float th = sub ? a.th_sub[gl] : a.th_pool[gl];
         for (int pix = tid; pix < res2; pix += 256) {
             const bool on = (pooled[pix] / mx) > th;
@@ -189,12 +241,11 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
     }
 }
 
-// dst[i] += src[i] for up to 32 fp16 tensors in ONE launch (AttentionStore.between_steps, utils/p2p.py:164-170: 32 stored maps)
-struct AccumArgs { half_t* dst[32]; const half_t* src[32]; long long n[32]; };
-__global__ __launch_bounds__(256) void accumulate_multi_kernel(AccumArgs a) {
-    const int t = blockIdx.y;
-    half_t* d = a.dst[t]; const half_t* s = a.src[t];
-    const long long n = a.n[t], n8 = n >> 3;
+// dst[i] += src[i] for many fp16 tensors in ONE launch (AttentionStore.between_steps, utils/p2p.py:164-170: 32 stored maps at SD1.5,
+// 130 at SDXL).  blockIdx.y = tensor; its pointers and count come from the kernel arguments (up to 32 tensors, host arrays) or from a
+// table in device memory: int64 [3][n] = dst pointers | src pointers | counts.
+__device__ __forceinline__ void accumulate_one(half_t* __restrict__ d, const half_t* __restrict__ s, long long n) {
+    const long long n8 = n >> 3;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
         f16x8 x = *reinterpret_cast<const f16x8*>(d + i * 8), y = *reinterpret_cast<const f16x8*>(s + i * 8);
 #pragma unroll
@@ -203,6 +254,15 @@ __global__ __launch_bounds__(256) void accumulate_multi_kernel(AccumArgs a) {
     }
     if (blockIdx.x == 0)
         for (long long i = (n8 << 3) + threadIdx.x; i < n; i += 256) d[i] = (half_t)((float)d[i] + (float)s[i]);
+}
+struct AccumArgs { half_t* dst[32]; const half_t* src[32]; long long n[32]; };
+__global__ __launch_bounds__(256) void accumulate_multi_kernel(AccumArgs a) {
+    const int t = blockIdx.y;
+    accumulate_one(a.dst[t], a.src[t], a.n[t]);
+}
+__global__ __launch_bounds__(256) void accumulate_table_kernel(const long long* __restrict__ table, int n_tensors) {
+    const int t = blockIdx.y;
+    accumulate_one(reinterpret_cast<half_t*>(table[t]), reinterpret_cast<const half_t*>(table[n_tensors + t]), table[2 * n_tensors + t]);
 }
 
 }  // namespace
@@ -226,27 +286,61 @@ extern "C" int icd_p2p_cross_edit(void* probs, int32_t n_prompts, int32_t heads,
     return icd_p2p_cross_edit_groups(probs, 1, n_prompts, heads, nq, nk, ld, At, D, stream);
 }
 
-extern "C" int icd_local_blend_groups(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
-                                      int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
-                                      const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
-                                      float* out, void* stream) {
+extern "C" int64_t icd_local_blend_workspace_bytes(int32_t n_groups, int32_t n_prompts, int32_t res) {
+    if (n_groups <= 0 || n_prompts <= 0 || res <= 0) return 0;
+    return (int64_t)n_groups * n_prompts * 2 * res * res * (int64_t)sizeof(float);
+}
+
+extern "C" int icd_local_blend_groups_ws(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
+                                         int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub,
+                                         const float* th_pool, const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32,
+                                         int32_t C, int32_t H, int32_t W, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     ICD_CHECK_ARG(maps && heads && alpha && x && out && th_pool && th_sub && flags, "icd_local_blend: null pointer");
-    ICD_CHECK_ARG(n_layers > 0 && n_layers <= 8 && n_groups > 0 && n_prompts > 0 && res > 0 && res * res <= 1024 && n_words > 0 && ld >= n_words,
-                  "icd_local_blend: 1..8 layers, res*res <= 1024, ld >= n_words");
+    ICD_CHECK_ARG(n_layers > 0 && n_layers <= BLEND_MAX_LAYERS && n_groups > 0 && n_prompts > 0 && res > 0 && res * res <= 1024 && n_words > 0 &&
+                      ld >= n_words,
+                  "icd_local_blend: 1..64 layers, res*res <= 1024, ld >= n_words");
     ICD_CHECK_ARG(C > 0 && H > 0 && W > 0, "icd_local_blend: empty latent");
-    for (int l = 0; l < n_layers; ++l) ICD_CHECK_ARG(maps[l] && heads[l] > 0, "icd_local_blend: layer %d has no maps", l);
-    for (int g = 0; g < n_groups; ++g)
+    long long total_heads = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        ICD_CHECK_ARG(maps[l] && heads[l] > 0, "icd_local_blend: layer %d has no maps", l);
+        total_heads += heads[l];
+    }
+    ICD_CHECK_ARG(total_heads <= 0x7fffffff, "icd_local_blend: too many heads");
+    bool any_sub = false, any_active = false;
+    for (int g = 0; g < n_groups; ++g) {
         ICD_CHECK_ARG(!(flags[g] & 2) || alpha_sub, "icd_local_blend_groups: group %d has substruct words but alpha_sub is NULL", g);
+        any_active |= (flags[g] & 1) != 0;
+        any_sub |= (flags[g] & 3) == 3;
+    }
+    const int res2 = res * res;
+    float* heat = nullptr;
+    if (workspace) {                                               // the reduce launch: every prompt's heat maps, once
+        ICD_CHECK_ARG(workspace_bytes >= icd_local_blend_workspace_bytes(n_groups, n_prompts, res) && (uintptr_t)workspace % 4 == 0,
+                      "icd_local_blend: workspace of %lld bytes, icd_local_blend_workspace_bytes asks for %lld", (long long)workspace_bytes,
+                      (long long)icd_local_blend_workspace_bytes(n_groups, n_prompts, res));
+        ICD_CHECK_ARG((long long)n_groups * n_prompts <= 65535, "icd_local_blend: at most 65535 prompts with a workspace");
+        heat = (float*)workspace;
+        if (any_active) {
+            HeatArgs h{};
+            for (int l = 0; l < n_layers; ++l) { h.maps[l] = (const half_t*)maps[l]; h.heads[l] = heads[l]; }
+            h.n_layers = n_layers; h.res2 = res2; h.n_words = n_words; h.ld = ld; h.total_heads = (int)total_heads;
+            h.alpha = alpha; h.alpha_sub = alpha_sub; h.heat = heat;
+            hipLaunchKernelGGL(local_blend_heat_kernel, dim3((res2 + HEAT_PIX - 1) / HEAT_PIX, n_groups * n_prompts, any_sub ? 2 : 1), dim3(256), 0,
+                               (hipStream_t)stream, h);
+            ICD_CHECK_LAUNCH("icd_local_blend(heat)");
+        }
+    }
     const long long per = (long long)C * H * W;
     for (int g0 = 0; g0 < n_groups; g0 += BLEND_MAX_GROUPS) {      // (launches in chunks of the groups the argument block holds)
         const int ng = std::min(n_groups - g0, BLEND_MAX_GROUPS);
         const long long s0 = (long long)g0 * n_prompts;            // first prompt of the chunk
         BlendArgs a{};
         for (int l = 0; l < n_layers; ++l) {
-            a.maps[l] = (const half_t*)maps[l] + s0 * heads[l] * res * res * ld; a.heads[l] = heads[l];
+            a.maps[l] = (const half_t*)maps[l] + s0 * heads[l] * res2 * ld; a.heads[l] = heads[l];
         }
         a.n_layers = n_layers; a.P = n_prompts; a.res = res; a.n_words = n_words; a.ld = ld;
         a.alpha = alpha + s0 * n_words; a.alpha_sub = alpha_sub ? alpha_sub + s0 * n_words : nullptr;
+        a.heat = heat ? heat + s0 * 2 * res2 : nullptr;
         a.x = x_is_f32 ? (const void*)((const float*)x + s0 * per) : (const void*)((const half_t*)x + s0 * per);
         a.x_f32 = x_is_f32; a.C = C; a.H = H; a.W = W; a.out = out + s0 * per;
         for (int g = 0; g < ng; ++g) { a.th_pool[g] = th_pool[g0 + g]; a.th_sub[g] = th_sub[g0 + g]; a.flags[g] = flags[g0 + g]; }
@@ -256,12 +350,24 @@ extern "C" int icd_local_blend_groups(const void* const* maps, const int32_t* he
     return ICD_OK;
 }
 
+extern "C" int icd_local_blend_groups(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_groups, int32_t n_prompts,
+                                      int32_t res, int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, const float* th_pool,
+                                      const float* th_sub, const int32_t* flags, const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W,
+                                      float* out, void* stream) {
+    return icd_local_blend_groups_ws(maps, heads, n_layers, n_groups, n_prompts, res, n_words, ld, alpha, alpha_sub, th_pool, th_sub, flags, x,
+                                     x_is_f32, C, H, W, out, nullptr, 0, stream);
+}
+
 extern "C" int icd_local_blend(const void* const* maps, const int32_t* heads, int32_t n_layers, int32_t n_prompts, int32_t res,
                                int32_t n_words, int32_t ld, const float* alpha, const float* alpha_sub, float th_pool, float th_sub,
                                const void* x, int32_t x_is_f32, int32_t C, int32_t H, int32_t W, float* out, void* stream) {
     const int32_t flags = 1 | (alpha_sub ? 2 : 0);
     return icd_local_blend_groups(maps, heads, n_layers, 1, n_prompts, res, n_words, ld, alpha, alpha_sub, &th_pool, &th_sub, &flags, x,
                                   x_is_f32, C, H, W, out, stream);
+}
+
+static unsigned accumulate_grid_x(long long nmax) {
+    return (unsigned)std::min<long long>(std::max<long long>((nmax / 8 + 255) / 256, 1), 512);
 }
 
 extern "C" int icd_accumulate_multi(void* const* dst, const void* const* src, const int64_t* counts, int32_t n_tensors, void* stream) {
@@ -274,8 +380,16 @@ extern "C" int icd_accumulate_multi(void* const* dst, const void* const* src, co
         a.dst[t] = (half_t*)dst[t]; a.src[t] = (const half_t*)src[t]; a.n[t] = counts[t];
         nmax = counts[t] > nmax ? counts[t] : nmax;
     }
-    const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((nmax / 8 + 255) / 256, 1), 512);
-    hipLaunchKernelGGL(accumulate_multi_kernel, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(accumulate_multi_kernel, dim3(accumulate_grid_x(nmax), n_tensors), dim3(256), 0, (hipStream_t)stream, a);
     ICD_CHECK_LAUNCH("icd_accumulate_multi");
+    return ICD_OK;
+}
+
+extern "C" int icd_accumulate_multi_n(const int64_t* table, int32_t n_tensors, int64_t max_count, void* stream) {
+    ICD_CHECK_ARG(table && n_tensors > 0 && n_tensors <= 65535 && max_count >= 0, "icd_accumulate_multi_n: 1..65535 tensors and a device table");
+    ICD_CHECK_ARG((uintptr_t)table % 8 == 0, "icd_accumulate_multi_n: the table is not 8-byte aligned");
+    hipLaunchKernelGGL(accumulate_table_kernel, dim3(accumulate_grid_x(max_count), n_tensors), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)table, (int)n_tensors);
+    ICD_CHECK_LAUNCH("icd_accumulate_multi_n");
     return ICD_OK;
 }

@@ -4,9 +4,10 @@ Kept: `sample_deterministic`, `inverse_sample_deterministic`, `DDIMSolver`, `pre
 `guidance_scale_embedding`, `linear_schedule_old`, `compute_embeddings`, `encode_prompt` - same signatures, same
 timestep / boundary construction, same per-step arithmetic (pinned by tests/golden/sdxl_loops.npz).
 
-Differences underneath: `pipe.unet` is the native executor (one call per step, no hooks on this path); the boundary
-step is the fused HIP kernel; per-step device constants are cached so the loop never synchronises.  One deliberate
-superset: with `use_dynamic_guidance=True` the reference only works for a batch of one (it builds
+Differences underneath: `pipe.unet` is the native executor (one call per step); the boundary step is the fused HIP kernel;
+per-step device constants are cached so the loop never synchronises.  Two deliberate supersets: `sample_deterministic(...,
+controller=)` runs the p2p controllers of the SD1.5 path on the SDXL batch (the reference's SDXL scripts register none), and
+with `use_dynamic_guidance=True` the reference only works for a batch of one (it builds
 `torch.tensor([tensor_of_len_B] * B)`, utils/generation_sdxl.py:439-440, which raises for B > 1); here the same scalar
 rule is applied to every sample, which is what the reference computes for B == 1.
 """
@@ -208,6 +209,19 @@ def _boundary_step(noise_pred, t, s, latents, prediction_type, alpha_schedule, s
                             prediction_type, alpha_schedule.to(dev), sigma_schedule.to(dev)).to(out_dtype)
 
 
+def _expand_edit_latents(latents, batch_size, groups):
+    """Latents of an edit: one sample for all prompts (init_latent of the SD1.5 runner), one per prompt group, or one per prompt."""
+    n = latents.shape[0]
+    if n == batch_size:
+        return latents
+    if n == 1:
+        return latents.expand(batch_size, *latents.shape[1:]).contiguous()
+    if groups is not None and n == groups[0]:
+        return latents.repeat_interleave(groups[1], 0)
+    raise ValueError(f"sample_deterministic: {n} latents for {batch_size} prompts"
+                     + ("" if groups is None else f" in {groups[0]} groups of {groups[1]}"))
+
+
 # --------------------------------------------------------------------------------------------- forward (inversion)
 def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scales=50, num_inference_steps=1, timesteps=None,
                                  start_timestep=19, max_inverse_timestep_index=49, return_start_latent=False,
@@ -251,8 +265,24 @@ def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scale
 def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=50, num_inference_steps=1, timesteps=None,
                          start_timestep=19, max_inverse_timestep_index=49, return_latent=False, guidance_scale=None,
                          compute_embeddings_fn=None, is_sdxl=False, endpoints=None, use_dynamic_guidance=False, tau1=0.7,
-                         tau2=0.7, amplify_prompt=None):
-    """Reverse consistency model: noise latents -> image (utils/generation_sdxl.py:324-473)."""
+                         tau2=0.7, amplify_prompt=None, *, controller=None):
+    """Reverse consistency model: noise latents -> image (utils/generation_sdxl.py:324-473).
+
+    controller (beyond the reference, whose SDXL scripts register none): a p2p controller - make_controller(...), AttentionStore, a
+    ControllerBatch - turns the call into a prompt-to-prompt edit of the batch [source, edit_1, ...].  It is registered on pipe.unet
+    (and stays registered, as after generation.runner: p2p.register_attention_control(pipe, None) detaches it), sees the whole batch
+    as conditional rows, gets `latents = controller.step_callback(latents)` after every boundary step, and the loop runs at the accurate
+    precision level.  `latents` may be one [1, 4, h, w] sample (usually inverse_sample_deterministic's output), expanded over the prompts.
+    Prompt groups as in generation.runner: `prompt` a list of G lists of P prompts with a p2p.ControllerBatch of G members, latents
+    [G, 4, h, w] (each repeated over its group) or [G * P, 4, h, w]."""
+    groups = None
+    if controller is not None:
+        from . import p2p
+        from .generation import _prompt_groups
+        groups = _prompt_groups(prompt, controller)
+        if groups is not None:
+            prompt = [p for grp in prompt for p in grp]
+        p2p.register_attention_control(pipe, controller)
     height = pipe.unet.config.sample_size * pipe.vae_scale_factor
     width = pipe.unet.config.sample_size * pipe.vae_scale_factor
     if prompt is not None and isinstance(prompt, str):
@@ -286,10 +316,17 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
         assert latents.dtype == pipe.unet.dtype
     else:
         latents = latents.to(prompt_embeds.dtype)
+        if controller is not None:
+            latents = _expand_edit_latents(latents, batch_size, groups)
     w_embedding = None if guidance_scale is None else _w_embedding([guidance_scale] * batch_size, latents.device, latents.dtype)
     ptype = pipe.scheduler.config.prediction_type
-    edit_ctx = _editing(pipe, use_dynamic_guidance)  # dynamic guidance = the reference's editing schedule: accurate precision level
+    # dynamic guidance = the reference's editing schedule, and a run with a controller is an edit: accurate precision level
+    edit_ctx = _editing(pipe, use_dynamic_guidance or controller is not None)
+    # every sample of an SDXL batch is conditional: the controller acts on the whole batch (the executor's cond-only hook layout)
+    hooked = controller is not None and hasattr(pipe.unet, "attn_cond_only")
     edit_ctx.__enter__()
+    if hooked:
+        was_cond_only, pipe.unet.attn_cond_only = pipe.unet.attn_cond_only, True
     try:
         for t, s in zip(timesteps.cpu(), boundary_timesteps.cpu()):
             if use_dynamic_guidance:
@@ -304,7 +341,11 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
             noise_pred = pipe.unet(latents, t, encoder_hidden_states=prompt_embeds, cross_attention_kwargs=None, return_dict=False,
                                    timestep_cond=w_embedding, added_cond_kwargs=encoded_text)[0]
             latents = _boundary_step(noise_pred, t, s, latents, ptype, alpha_schedule, sigma_schedule, pipe.unet.dtype)
+            if controller is not None:
+                latents = controller.step_callback(latents).to(pipe.unet.dtype)
     finally:
+        if hooked:
+            pipe.unet.attn_cond_only = was_cond_only
         edit_ctx.__exit__(None, None, None)
 
     vae = getattr(pipe, "vae", None)

@@ -562,34 +562,25 @@ def x0_step(x, eps, coef, out_dtype=None):
     return out
 
 
+BLEND_MAX_LAYERS = 64          # icd_local_blend*: layers per call (csrc/p2p.hip)
+
+
 def local_blend(maps, alpha, alpha_sub, th_pool, th_sub, x_t, res=16):
-    """LocalBlend in one launch (icd_local_blend).  maps: list of <= 8 fp16 cuda tensors [P*heads_l, res*res, n_words] (last dim
+    """LocalBlend (icd_local_blend_groups_ws, one group).  maps: list of <= 64 fp16 cuda tensors [P*heads_l, res*res, n_words] (last dim
     contiguous, rows evenly strided), alpha / alpha_sub: fp32 [P, n_words] word masks, x_t: [P, C, H, W] fp16 / fp32 -> fp32."""
-    P = alpha.shape[0]
-    n_words = alpha.shape[1]
-    assert x_t.is_cuda and x_t.is_contiguous() and x_t.dtype in (torch.float16, torch.float32) and x_t.shape[0] == P
-    ld = maps[0].stride(1)
-    ptrs, heads = (C.c_void_p * len(maps))(), (C.c_int32 * len(maps))()
-    for i, m in enumerate(maps):
-        assert m.is_cuda and m.dtype == torch.float16 and m.dim() == 3 and m.shape[1] == res * res and m.shape[2] == n_words
-        assert m.stride(2) == 1 and m.stride(1) == ld and m.stride(0) == res * res * ld and m.shape[0] % P == 0
-        ptrs[i], heads[i] = m.data_ptr(), m.shape[0] // P
-    al = alpha.to(device=x_t.device, dtype=torch.float32).contiguous()
-    als = None if alpha_sub is None else alpha_sub.to(device=x_t.device, dtype=torch.float32).contiguous()
-    out = torch.empty(x_t.shape, device=x_t.device, dtype=torch.float32)
-    _lib.check(_lib.load().icd_local_blend(ptrs, heads, len(maps), P, res, n_words, ld, _p(al), None if als is None else _p(als),
-                                           float(th_pool), float(th_sub), _p(x_t), int(x_t.dtype == torch.float32), x_t.shape[1],
-                                           x_t.shape[2], x_t.shape[3], _p(out), _stream()), "icd_local_blend")
-    return out
+    sub = None if alpha_sub is None else (alpha_sub, [True])
+    return local_blend_groups(maps, alpha, sub, [th_pool], [th_sub], [True], x_t, 1, res=res)
 
 
 def local_blend_groups(maps, alpha, alpha_sub, th_pool, th_sub, active, x_t, n_groups, res=16):
-    """LocalBlend for n_groups prompt groups of P in one launch (icd_local_blend_groups).  maps: list of <= 8 fp16 cuda tensors
-    [G*P*heads_l, res*res, n_words]; alpha fp32 [G*P, n_words]; alpha_sub fp32 [G*P, n_words] or None, with a list of G booleans
-    (which groups have substruct words) as its companion: alpha_sub = (tensor, has_sub); th_pool / th_sub / active: G values each;
-    x_t [G*P, C, H, W] fp16 / fp32 -> fp32.  Inactive groups come back unchanged."""
+    """LocalBlend for n_groups prompt groups of P (icd_local_blend_groups_ws: a reduce launch builds every prompt's heat map once, a second
+    launch pools, thresholds and blends).  maps: list of <= 64 fp16 cuda tensors [G*P*heads_l, res*res, n_words]; alpha fp32 [G*P, n_words];
+    alpha_sub fp32 [G*P, n_words] or None, with a list of G booleans (which groups have substruct words) as its companion: alpha_sub =
+    (tensor, has_sub); th_pool / th_sub / active: G values each; x_t [G*P, C, H, W] fp16 / fp32 -> fp32.  Inactive groups come back
+    unchanged."""
     GP, n_words = alpha.shape
     assert GP % n_groups == 0 and len(th_pool) == len(th_sub) == len(active) == n_groups
+    assert 0 < len(maps) <= BLEND_MAX_LAYERS, f"local_blend: 1..{BLEND_MAX_LAYERS} layers (got {len(maps)})"
     P = GP // n_groups
     assert x_t.is_cuda and x_t.is_contiguous() and x_t.dtype in (torch.float16, torch.float32) and x_t.shape[0] == GP
     ld = maps[0].stride(1)
@@ -606,23 +597,33 @@ def local_blend_groups(maps, alpha, alpha_sub, th_pool, th_sub, active, x_t, n_g
     tp, ts = (C.c_float * n_groups)(*map(float, th_pool)), (C.c_float * n_groups)(*map(float, th_sub))
     fl = (C.c_int32 * n_groups)(*[int(bool(a)) | (2 if s else 0) for a, s in zip(active, has_sub)])
     out = torch.empty(x_t.shape, device=x_t.device, dtype=torch.float32)
-    _lib.check(_lib.load().icd_local_blend_groups(ptrs, heads, len(maps), n_groups, P, res, n_words, ld, _p(al), _p(als), tp, ts, fl,
-                                                  _p(x_t), int(x_t.dtype == torch.float32), x_t.shape[1], x_t.shape[2], x_t.shape[3],
-                                                  _p(out), _stream()), "icd_local_blend_groups")
+    lib = _lib.load()
+    ws = torch.empty((lib.icd_local_blend_workspace_bytes(n_groups, P, res) // 4,), device=x_t.device, dtype=torch.float32)
+    _lib.check(lib.icd_local_blend_groups_ws(ptrs, heads, len(maps), n_groups, P, res, n_words, ld, _p(al), _p(als), tp, ts, fl,
+                                             _p(x_t), int(x_t.dtype == torch.float32), x_t.shape[1], x_t.shape[2], x_t.shape[3],
+                                             _p(out), _p(ws), ws.numel() * 4, _stream()), "icd_local_blend_groups_ws")
     return out
 
 
 def accumulate_multi(dst, src):
-    """dst[t] += src[t] for lists of fp16 cuda tensors (<= 32 per launch), rounded like torch's in-place add."""
+    """dst[t] += src[t] for lists of fp16 cuda tensors in one launch, rounded like torch's in-place add.  Up to 32 tensors travel in the
+    kernel's arguments (icd_accumulate_multi); more - an SDXL step stores 130 maps - in a table on the device (icd_accumulate_multi_n)."""
     lib = _lib.load()
-    for i in range(0, len(dst), 32):
-        d, s = dst[i:i + 32], src[i:i + 32]
-        n = len(d)
+    n = len(dst)
+    assert n == len(src) and n > 0
+    for a, b in zip(dst, src):
+        assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float16 and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+    if n <= 32:
         dp, sp, cn = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
-        for t, (a, b) in enumerate(zip(d, s)):
-            assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float16 and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+        for t, (a, b) in enumerate(zip(dst, src)):
             dp[t], sp[t], cn[t] = a.data_ptr(), b.data_ptr(), a.numel()
         _lib.check(lib.icd_accumulate_multi(dp, sp, cn, n, _stream()), "icd_accumulate_multi")
+        return
+    assert all(a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 for a, b in zip(dst, src)), "accumulate_multi: 16-byte aligned tensors"
+    counts = [a.numel() for a in dst]
+    table = torch.tensor([[a.data_ptr() for a in dst], [b.data_ptr() for b in src], counts], dtype=torch.int64).to(dst[0].device)
+    # (the table's memory goes back to torch's allocator when this returns: a later user of it on this stream runs after the launch)
+    _lib.check(lib.icd_accumulate_multi_n(_p(table), n, max(counts), _stream()), "icd_accumulate_multi_n")
 
 
 # ------------------------------------------------------------------------------------------------ image ingest (csrc/ingest.hip)

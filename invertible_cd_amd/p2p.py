@@ -14,7 +14,8 @@ probabilities must be materialised at all:
     controller, utils/p2p.py:147,184-188) run the fused flash kernel and only tick the controller's counters;
   * when the sampler eliminated the dead unconditional half of the CFG batch (utils/generation.py:247-251 discards it
     when w_embed_dim > 0) the controller's `forward` - which in the reference only ever sees the conditional half,
-    utils/p2p.py:106-107 - is applied to the whole (cond-only) tensor.
+    utils/p2p.py:106-107 - is applied to the whole (cond-only) tensor.  The SDXL sampler (generation_sdxl.sample_deterministic
+    with `controller=`) always runs this layout: its batch [source, edit_1, ...] has no unconditional half at all.
 """
 import abc
 from typing import Dict, List, Optional, Tuple, Union
@@ -34,7 +35,12 @@ tokenizer = None
 
 # ------------------------------------------------------------------------------------------- latent blending
 class LocalBlend:
-    """Word-localised latent blending from the accumulated 16x16 cross-attention maps (utils/p2p.py:18-70)."""
+    """Word-localised latent blending from the accumulated cross-attention maps (utils/p2p.py:18-70).
+
+    The reference reads down_cross[2:4] + up_cross[:3] as 16 x 16 maps against a 64 x 64 latent.  Those are exactly the stored
+    cross-attention maps of the down and up places whose side is a quarter of the latent's, and that is the rule here (`select_maps`):
+    SD1.5 at 64 x 64 latents gives the same five maps in the same order; SDXL at 128 x 128 latents gives its 1024-query layers as
+    32 x 32 maps, 20 down + 30 up (the mid block works at an eighth and stays out, as in SD1.5)."""
 
     def __init__(self, prompts: List[str], words, substruct_words=None, start_blend=0.2, th=(.3, .3)):
         self.alpha_layers = self._word_mask(prompts, words).to(device)
@@ -52,21 +58,40 @@ class LocalBlend:
         return mask
 
     @staticmethod
-    def _on_device(x_t, layers):
-        """The HIP kernel takes the accumulated store tensors as they are: fp16 on the GPU, [P*heads, 256, 77] with evenly
-        strided rows.  Anything else (CPU goldens, foreign dtypes) takes the torch expression below."""
-        if not (x_t.is_cuda and x_t.dim() == 4 and x_t.dtype in (torch.float16, torch.float32)):
+    def select_maps(attention_store, x_t):
+        """(maps, (rows, cols)): the stored down / up cross-attention maps at a quarter of the latent's side, in store order."""
+        rows, cols = x_t.shape[2] // 4, x_t.shape[3] // 4
+        down, up = attention_store["down_cross"], attention_store["up_cross"]
+        ref = down[2:4] + up[:3]
+        if len(down) <= 4 and len(up) <= 6 and ref and all(m.shape[1] == rows * cols for m in ref):
+            # a store no larger than SD1.5's (4 down + 6 up maps kept): the reference's own positions.  On SD1.5 they ARE the quarter-side
+            # maps; a smaller store (the golden walk of tests/golden/p2p.npz keeps three 16 x 16 maps per place) is read as the reference
+            # reads it, position by position, so every vector captured from the reference stays what it was.
+            return ref, (rows, cols)
+        maps = [m for m in down + up if m.shape[1] == rows * cols]
+        if rows * cols == 0 or not maps:
+            raise ValueError(f"LocalBlend: the store holds no down / up cross-attention map of {rows} x {cols} queries (a quarter of the "
+                             f"{x_t.shape[2]} x {x_t.shape[3]} latent's side); stored: "
+                             f"{sorted({m.shape[1] for m in attention_store['down_cross'] + attention_store['up_cross']})}")
+        return maps, (rows, cols)
+
+    @staticmethod
+    def _on_device(x_t, layers, side=(16, 16)):
+        """The HIP kernels take the accumulated store tensors as they are: fp16 on the GPU, [P*heads, res*res, 77] with evenly strided
+        rows, res <= 32, up to 64 layers.  Anything else (CPU goldens, foreign dtypes, non-square maps) takes the torch expression below."""
+        n = side[0] * side[1]
+        if not (x_t.is_cuda and x_t.dim() == 4 and x_t.dtype in (torch.float16, torch.float32) and side[0] == side[1] and 0 < n <= 1024):
             return False
         for m in layers:
-            if not (m.is_cuda and m.dtype == torch.float16 and m.dim() == 3 and m.shape[1] == 256 and m.shape[2] == MAX_NUM_WORDS
-                    and m.stride(2) == 1 and m.stride(1) == layers[0].stride(1) and m.stride(0) == 256 * m.stride(1)):
+            if not (m.is_cuda and m.dtype == torch.float16 and m.dim() == 3 and m.shape[1] == n and m.shape[2] == MAX_NUM_WORDS
+                    and m.stride(2) == 1 and m.stride(1) == layers[0].stride(1) and m.stride(0) == n * m.stride(1)):
                 return False
-        return len(layers) <= 8
+        return len(layers) <= 64
 
     def get_mask(self, maps, alpha, use_pool, x_t):
-        """Word-weighted mean over layers x heads of the 16x16 maps -> (3x3 max-pool) -> nearest resize to the latent ->
+        """Word-weighted mean over layers x heads of the maps -> (3x3 max-pool) -> nearest resize to the latent ->
         per-prompt max normalisation -> threshold; every prompt's mask is OR-ed with the base prompt's (utils/p2p.py:20-31)."""
-        heat = (maps * alpha).sum(-1).mean(1)                              # [P, 1, 16, 16]
+        heat = (maps * alpha).sum(-1).mean(1)                              # [P, 1, res, res]
         if use_pool:
             heat = nnf.max_pool2d(heat, kernel_size=3, stride=1, padding=1)
         heat = nnf.interpolate(heat, size=(x_t.shape[2:]))
@@ -75,8 +100,8 @@ class LocalBlend:
         return on[:1] + on
 
     def __call__(self, x_t, attention_store):
-        """`x_t[e] <- x_t[0] + mask[e] * (x_t[e] - x_t[0])` from the accumulated 16x16 cross-attention maps of
-        down_cross[2:4] + up_cross[:3] (utils/p2p.py:33-44)."""
+        """`x_t[e] <- x_t[0] + mask[e] * (x_t[e] - x_t[0])` from the accumulated quarter-side cross-attention maps
+        (utils/p2p.py:33-44: down_cross[2:4] + up_cross[:3] at 16 x 16)."""
         self.counter += 1
         if self.counter <= self.start_blend:
             return x_t
@@ -85,15 +110,15 @@ class LocalBlend:
     def blend(self, x_t, attention_store):
         """The blend itself, past start_blend (what __call__ does after advancing its counter)."""
         n_prompts = self.alpha_layers.shape[0]
-        layers = attention_store["down_cross"][2:4] + attention_store["up_cross"][:3]
-        if self._on_device(x_t, layers):
-            # one HIP launch (icd_local_blend): word-weighted mean of the maps, pool, normalise, threshold, OR with the base
-            # prompt's mask, substruct words, nearest resize and the blend itself
+        layers, side = self.select_maps(attention_store, x_t)
+        if self._on_device(x_t, layers, side):
+            # two HIP launches (icd_local_blend_groups_ws): word-weighted mean of the maps; pool, normalise, threshold, OR with the
+            # base prompt's mask, substruct words, nearest resize and the blend itself
             from . import ops
             sub = None if self.substruct_layers is None else self.substruct_layers.reshape(n_prompts, MAX_NUM_WORDS)
             return ops.local_blend(layers, self.alpha_layers.reshape(n_prompts, MAX_NUM_WORDS), sub, self.th[0], self.th[1],
-                                   x_t.contiguous())
-        maps = torch.cat([m.reshape(n_prompts, -1, 1, 16, 16, MAX_NUM_WORDS) for m in layers], dim=1)
+                                   x_t.contiguous(), res=side[0])
+        maps = torch.cat([m.reshape(n_prompts, -1, 1, side[0], side[1], MAX_NUM_WORDS) for m in layers], dim=1)
         mask = self.get_mask(maps, self.alpha_layers, True, x_t)
         if self.substruct_layers is not None:
             mask = mask * ~self.get_mask(maps, self.substruct_layers, False, x_t)
@@ -503,11 +528,11 @@ class ControllerBatch(AttentionStore):
             active.append(lb is not None and lb.counter > lb.start_blend)
         if not any(active):
             return x_t
-        layers = self.attention_store["down_cross"][2:4] + self.attention_store["up_cross"][:3]
-        if LocalBlend._on_device(x_t, layers) and all(lb is None or lb.alpha_layers.shape[0] == P for lb in lbs):
+        layers, side = LocalBlend.select_maps(self.attention_store, x_t)
+        if LocalBlend._on_device(x_t, layers, side) and all(lb is None or lb.alpha_layers.shape[0] == P for lb in lbs):
             from . import ops
             alpha, sub, th_pool, th_sub = self._blend_terms(lbs, x_t.device)
-            return ops.local_blend_groups(layers, alpha, sub, th_pool, th_sub, active, x_t.contiguous(), G)
+            return ops.local_blend_groups(layers, alpha, sub, th_pool, th_sub, active, x_t.contiguous(), G, res=side[0])
         outs = []
         for g, (m, lb, on) in enumerate(zip(self.members, lbs, active)):
             xg = x_t[g * P:(g + 1) * P]
