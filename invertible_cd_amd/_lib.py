@@ -287,27 +287,26 @@ def profile_read():
             for r in rows[:n]}
 
 
-def profile_dump():
-    """Per-launch records [(family, M, N, K, aux, ms, flops)] - call after synchronising the stream."""
+def _profile_records():
+    """Every icd_profile_record of the launches recorded so far, in launch order."""
     lib = load()
     n = lib.icd_profile_dump(None, 0)
     recs = (ProfileRecord * max(n, 1))()
     n = lib.icd_profile_dump(recs, n)
     if n < 0:
         check(n, "icd_profile_dump")
-    return [(PROF_KINDS[r.kind], r.M, r.N, r.K, r.aux, r.ms, r.flops) for r in recs[:n]]
+    return recs[:n]
+
+
+def profile_dump():
+    """Per-launch records [(family, M, N, K, aux, ms, flops)] - call after synchronising the stream."""
+    return [(PROF_KINDS[r.kind], r.M, r.N, r.K, r.aux, r.ms, r.flops) for r in _profile_records()]
 
 
 def profile_plans():
     """Per-launch planner records of the GEMM families: dicts with family, M, N, K, aux, tile (m, n), big (gemm_big.hip tile),
     ln_inline (LayerNorm statistics in the main loop), xattn (fused cross-attention epilogue), ksplit - what a test asserts when
     it claims a forward took a given code path.  Call after synchronising the stream."""
-    lib = load()
-    n = lib.icd_profile_dump(None, 0)
-    recs = (ProfileRecord * max(n, 1))()
-    n = lib.icd_profile_dump(recs, n)
-    if n < 0:
-        check(n, "icd_profile_dump")
     return [dict(family=PROF_KINDS[r.kind], M=r.M, N=r.N, K=r.K, aux=r.aux, ms=r.ms, tile=(r.tile_m, r.tile_n),
                  big=bool(r.plan_flags & 1), ln_inline=bool(r.plan_flags & 2), xattn=bool(r.plan_flags & 4), ksplit=r.ksplit)
-            for r in recs[:n] if r.tile_m > 0]
+            for r in _profile_records() if r.tile_m > 0]

@@ -8,99 +8,22 @@
 //
 // Layout: activations fp16 token-major [B, H*W, C]; skip concat is folded into the consumers' loaders (never
 // materialised); V is produced transposed by the to_v GEMM epilogue; all ResnetBlock2D time projections are ONE GEMM.
+//
+// This file: struct icd_unet (configuration, bound tensors, options), Exec (one forward: forward() is the walk, one member function per
+// block below it) and the icd_unet_* entries.  Every icd_gemm launch is a descriptor from dense() / conv() with its optional fields set
+// by name at the call site, then launch().  The allocator is arena.h, the launch timing profile.h.
 #include <string>
 #include <unordered_map>
 #include <vector>
 #include <algorithm>
 #include <string.h>
 #include "common.h"
+#include "arena.h"
+#include "profile.h"
 
 namespace {
 
 struct Tensor { const void* ptr; int dtype; long long numel; };
-
-// ---- per-family launch timing (HIP events on the launch stream) ------------------------------------------------
-struct ProfRec { hipEvent_t a, b; int kind; double flops, bytes; int M, N, K, aux; int tile_m, tile_n, plan_flags, ksplit; double xflops; };
-bool g_prof_on = false;
-unsigned g_prof_mask = 0xffffffffu;     // bit k: record launches of family k
-std::vector<ProfRec> g_prof;
-std::vector<hipEvent_t> g_ev_pool;
-
-hipEvent_t prof_event() {
-    if (!g_ev_pool.empty()) { hipEvent_t e = g_ev_pool.back(); g_ev_pool.pop_back(); return e; }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    return e;
-}
-struct ProfScope {
-    bool on; hipStream_t st; size_t idx;
-    ProfScope(bool active, hipStream_t s, int kind, double flops, double bytes, int M = 0, int N = 0, int K = 0, int aux = 0)
-        : on(active && g_prof_on && ((g_prof_mask >> kind) & 1u)), st(s), idx(0) {
-        if (!on) return;
-        ProfRec r{prof_event(), prof_event(), kind, flops, bytes, M, N, K, aux, 0, 0, 0, 0, flops};
-        (void)hipEventRecord(r.a, st);
-        idx = g_prof.size();
-        g_prof.push_back(r);
-    }
-    ~ProfScope() { if (on) (void)hipEventRecord(g_prof[idx].b, st); }
-    void executed(double xf) { if (on) g_prof[idx].xflops = xf; }      // flops issued to the matrix cores when they differ from the algorithmic count
-    void plan(const icd_gemm_desc& d) {          // which tile the planner takes for this launch (tests assert the code path)
-        if (!on) return;
-        icd_gemm_plan_info pi;
-        if (icd_gemm_plan(&d, &pi) != ICD_OK) return;
-        ProfRec& r = g_prof[idx];
-        r.tile_m = pi.tile_m; r.tile_n = pi.tile_n; r.ksplit = pi.ksplit;
-        r.plan_flags = (pi.kernel ? 1 : 0) | (pi.ln_inline ? 2 : 0) | (pi.xattn ? 4 : 0);
-    }
-};
-
-struct Arena {
-    char* base = nullptr;
-    long long cap = 0, peak = 0;
-    bool dry = false;
-    struct Blk { long long off, size; };
-    std::vector<Blk> free_list;   // sorted by offset
-    std::vector<Blk> live;
-    void reset(void* b, long long c, bool d) {
-        base = (char*)b; cap = c; dry = d; peak = 0;
-        free_list.clear(); live.clear();
-        free_list.push_back({0, d ? (1LL << 60) : c});
-    }
-    void* alloc(long long bytes) {
-        bytes = (bytes + 255) & ~255LL;
-        if (bytes == 0) bytes = 256;
-        for (size_t i = 0; i < free_list.size(); ++i) {
-            if (free_list[i].size >= bytes) {
-                const long long off = free_list[i].off;
-                free_list[i].off += bytes; free_list[i].size -= bytes;
-                if (free_list[i].size == 0) free_list.erase(free_list.begin() + i);
-                live.push_back({off, bytes});
-                peak = std::max(peak, off + bytes);
-                return (dry ? (char*)0x100000 : base) + off;
-            }
-        }
-        return nullptr;
-    }
-    void release(void* p) {
-        if (!p) return;
-        const long long off = (char*)p - (dry ? (char*)0x100000 : base);
-        for (size_t i = 0; i < live.size(); ++i)
-            if (live[i].off == off) {
-                Blk b = live[i];
-                live.erase(live.begin() + i);
-                auto it = std::lower_bound(free_list.begin(), free_list.end(), b,
-                                           [](const Blk& x, const Blk& y) { return x.off < y.off; });
-                it = free_list.insert(it, b);
-                if (it + 1 != free_list.end() && it->off + it->size == (it + 1)->off) {
-                    it->size += (it + 1)->size; free_list.erase(it + 1);
-                }
-                if (it != free_list.begin() && (it - 1)->off + (it - 1)->size == it->off) {
-                    (it - 1)->size += it->size; free_list.erase(it);
-                }
-                return;
-            }
-    }
-};
 
 }  // namespace
 
@@ -215,8 +138,51 @@ struct Exec {
     bool ok() const { return status == ICD_OK; }
     void run(int rc) { if (rc != ICD_OK && status == ICD_OK) status = rc; }
 
-    // ---------------------------------------------------------------------------------------------- op wrappers
-    void gemm_desc(icd_gemm_desc& d) {
+    // ---------------------------------------------------------------------------------------------- descriptors and launches
+    // The two constructors take what every launch has; bias, resid / ldr, rowbias / ld_rowbias, ln_stats / ln_colsum, flags,
+    // rows_per_sample and the twin / carry pair (set_aux) are set by their icd_gemm_desc names at the call site.
+    // dense: out[M, N] (ldo) = a[M, K] (lda) @ w[N, K]^T
+    static icd_gemm_desc dense(const void* a, int lda, long long M, int K, const half_t* w, int N, void* out, int ldo) {
+        icd_gemm_desc d; memset(&d, 0, sizeof(d));
+        d.a0 = a; d.w = w; d.out = out;
+        d.M = (int)M; d.N = N; d.K = K; d.Nw = N; d.lda = lda; d.ldw = K; d.ldo = ldo;
+        d.mode = 0; d.batch = 1; d.zdiv = 1; d.alpha = 1.f;
+        return d;
+    }
+    // conv: out[B Ho Wo, Cout] = im2col(cat(x0, x1)) @ w^T, ksize x ksize taps on the (optionally nearest-2x upsampled) input grid
+    icd_gemm_desc conv(const Act& x0, const Act* x1, int Hin, int Win, int ksize, int stride, int upsample, const half_t* w, int Cout, void* out) const {
+        icd_gemm_desc d; memset(&d, 0, sizeof(d));
+        const int Hu = Hin << upsample, Wu = Win << upsample;
+        const int Ho = (Hu + stride - 1) / stride, Wo = (Wu + stride - 1) / stride;
+        d.a0 = x0.p; d.a1 = x1 ? x1->p : nullptr; d.w = w; d.out = out;
+        d.C0 = x0.C; d.C1 = x1 ? x1->C : 0;
+        d.M = B * Ho * Wo; d.N = Cout; d.K = ksize * ksize * (d.C0 + d.C1); d.Nw = Cout;
+        d.ldw = d.K; d.ldo = Cout; d.ldr = Cout; d.rows_per_sample = Ho * Wo;
+        d.mode = 1; d.Hin = Hin; d.Win = Win; d.Hout = Ho; d.Wout = Wo; d.ksize = ksize; d.stride = stride; d.upsample = upsample;
+        d.batch = 1; d.zdiv = 1; d.alpha = 1.f;
+        return d;
+    }
+    // phase = 2 py + px: one pixel phase of the nearest-2x upsampling conv in its 2 x 2 form on the input grid (icd_gemm_desc.conv_ktaps);
+    // d is the stride-1 3 x 3 conv on that grid
+    static void conv_phase(icd_gemm_desc& d, int phase) {
+        const int py = phase >> 1, px = phase & 1;
+        d.conv_tap_base = 3 * py + px; d.conv_ktaps = 4; d.K = 4 * (d.C0 + d.C1); d.ldw = d.K;
+        d.out_remap_w = d.Wout; d.out_remap_c = 2 * py * d.Wout + px;
+    }
+    // resid_aux / out_aux: the fp32 twin or the error carry of `resid` / `out` (residual mode 1 / 2; same leading dimensions).  Call it
+    // after d.resid is set: in mode 1 the fp32 twin IS the residual and replaces the fp16 one.
+    void set_aux(icd_gemm_desc& d, const void* resid_aux, void* out_aux) const {
+        if (u->resid_mode == 1) {
+            if (resid_aux) { d.resid = resid_aux; d.flags |= ICD_GEMM_RESID_F32; }
+            d.out_f32 = (float*)out_aux;
+        } else {
+            d.resid_carry = resid_aux; d.out_carry = out_aux;
+        }
+    }
+    long long aux_bytes(long long elems) const { return u->resid_mode == 1 ? elems * 4 : elems; }
+    void* alloc_aux(long long elems) { return u->resid_mode ? (void*)alloc<char>(aux_bytes(elems)) : nullptr; }
+    // alg_k: the algorithmic K of the operator where it differs from the K the launch issues (split operands, the phase form)
+    void launch(icd_gemm_desc& d, long long alg_k = 0) {
         // split-K scratch for small-M / deep-K shapes comes from the arena (accounted for in the dry run too)
         void* ws = nullptr;
         const bool splittable = (d.batch <= 1) && !(d.flags & (ICD_GEMM_OUT_TRANS | ICD_GEMM_GEGLU));
@@ -229,76 +195,12 @@ struct Exec {
         // launches (K doubled by the lo segment) and the phase form of the upsampling conv (4 of 9 taps) issue a different number
         const double xf = 2.0 * d.M * (double)d.N * d.K * nb;
         const double af = alg_k > 0 ? 2.0 * d.M * (double)d.N * alg_k : xf;
-        alg_k = 0;
-        ProfScope ps(true, st, d.mode == 1 ? ICD_PROF_GEMM_CONV : (nb > 1 ? ICD_PROF_GEMM_BATCHED : ICD_PROF_GEMM_DENSE),
+        ProfScope ps(st, d.mode == 1 ? ICD_PROF_GEMM_CONV : (nb > 1 ? ICD_PROF_GEMM_BATCHED : ICD_PROF_GEMM_DENSE),
                      af, 0.0, d.M, d.N, d.K, d.mode == 1 ? d.ksize * 100 + d.stride * 10 + d.upsample : d.flags);
         ps.executed(xf);
         d.flags |= u->gemm_tune;
         ps.plan(d);
         run(icd_gemm(&d, st));
-    }
-    // dense: out[M,N] (ldo) = a[M,K](lda) @ w[N,K]^T + bias + resid
-    // resid_aux / out_aux: the fp32 twin or the error carry of `resid` / `out` (residual mode 1 / 2; same leading dimensions)
-    void set_aux(icd_gemm_desc& d, const void* resid_aux, void* out_aux) {
-        if (u->resid_mode == 1) {
-            if (resid_aux) { d.resid = resid_aux; d.flags |= ICD_GEMM_RESID_F32; }       // the fp32 twin IS the residual
-            d.out_f32 = (float*)out_aux;
-        } else {
-            d.resid_carry = resid_aux; d.out_carry = out_aux;
-        }
-    }
-    long long aux_bytes(long long elems) const { return u->resid_mode == 1 ? elems * 4 : elems; }
-    void* alloc_aux(long long elems) { return u->resid_mode ? (void*)alloc<char>(aux_bytes(elems)) : nullptr; }
-    void linear(const half_t* a, int lda, int M, int K, const half_t* w, int N, const float* bias, const half_t* resid,
-                int ldr, half_t* out, int ldo, int flags = 0, int rps = 0, const float* ln_stats = nullptr,
-                const float* ln_colsum = nullptr, const void* resid_aux = nullptr, void* out_aux = nullptr) {
-        icd_gemm_desc d; memset(&d, 0, sizeof(d));
-        d.a0 = a; d.w = w; d.bias = bias; d.resid = resid; d.out = out;
-        d.flags = flags;
-        set_aux(d, resid_aux, out_aux);
-        flags = d.flags;
-        d.ln_stats = ln_stats; d.ln_colsum = ln_colsum;
-        d.M = M; d.N = N; d.K = K; d.Nw = N; d.lda = lda; d.ldw = K; d.ldo = ldo; d.ldr = ldr;
-        d.rows_per_sample = rps; d.mode = 0; d.batch = 1; d.zdiv = 1; d.alpha = 1.f; d.flags = flags;
-        gemm_desc(d);
-    }
-    // h <- h + FF(LN(h)) in place (icd_ffn_geglu); resid: h or null (fp32 twin: hx is the residual), hx: twin / carry of the stream
-    void ffn_fused(half_t* h, int M, int C, const half_t* w1, const float* b1, const float* lnsum, float* lnst, int lnc, const half_t* w2,
-                   const float* b2, const half_t* resid, void* hx) {
-        if (!ok() || dry) return;
-        icd_ffn_desc f; memset(&f, 0, sizeof(f));
-        f.x = h; f.w1 = w1; f.b1 = b1; f.w2 = w2; f.b2 = b2; f.resid = resid; f.out = h;
-        f.M = M; f.C = C; f.hidden = 4 * C; f.ldx = C; f.ldw1 = C; f.ldw2 = 4 * C; f.ldo = C; f.ldr = C;
-        f.flags = lnc; f.ln_stats = lnst; f.ln_colsum = lnsum;
-        if (u->resid_mode == 1) { f.resid = hx; f.flags |= ICD_GEMM_RESID_F32; f.out_f32 = (float*)hx; }
-        else { f.resid_carry = hx; f.out_carry = hx; }
-        // family gemm_dense with the algorithmic flops of the two projections it replaces; no tile record (not a planner launch)
-        ProfScope ps(true, st, ICD_PROF_GEMM_DENSE, 2.0 * M * (double)C * (8.0 * C + 4.0 * C), 0.0, M, C, 4 * C, ICD_GEMM_GEGLU);
-        run(icd_ffn_geglu(&f, st));
-    }
-    // resid_aux / out_aux: as in linear(); out_is_f32: `out` itself is float (residual mode 1: the shortcut conv of a ResnetBlock2D,
-    // which is only ever a residual)
-    // phase: -1, or 2 py + px - one pixel phase of the nearest-2x upsampling conv in its 2 x 2 form on the input grid (icd_gemm_desc.conv_ktaps)
-    void conv(const Act& x0, const Act* x1, int Hin, int Win, int ksize, int stride, int upsample, const half_t* w, int Cout,
-              const float* bias, const half_t* rowbias, int ld_rowbias, const half_t* resid, void* out, const void* resid_aux = nullptr,
-              void* out_aux = nullptr, bool out_is_f32 = false, int phase = -1) {
-        icd_gemm_desc d; memset(&d, 0, sizeof(d));
-        const int Hu = Hin << upsample, Wu = Win << upsample;
-        const int Ho = (Hu + stride - 1) / stride, Wo = (Wu + stride - 1) / stride;
-        d.a0 = x0.p; d.a1 = x1 ? x1->p : nullptr; d.w = w; d.bias = bias; d.rowbias = rowbias; d.resid = resid; d.out = out;
-        d.C0 = x0.C; d.C1 = x1 ? x1->C : 0;
-        d.M = B * Ho * Wo; d.N = Cout; d.K = ksize * ksize * (d.C0 + d.C1); d.Nw = Cout;
-        d.ldw = d.K; d.ldo = Cout; d.ldr = Cout; d.ld_rowbias = ld_rowbias; d.rows_per_sample = Ho * Wo;
-        d.mode = 1; d.Hin = Hin; d.Win = Win; d.Hout = Ho; d.Wout = Wo; d.ksize = ksize; d.stride = stride; d.upsample = upsample;
-        d.batch = 1; d.zdiv = 1; d.alpha = 1.f;
-        if (phase >= 0) {
-            const int py = phase >> 1, px = phase & 1;
-            d.conv_tap_base = 3 * py + px; d.conv_ktaps = 4; d.K = 4 * (d.C0 + d.C1); d.ldw = d.K;
-            d.out_remap_w = Wo; d.out_remap_c = 2 * py * Wo + px;
-        }
-        set_aux(d, resid_aux, out_aux);
-        if (out_is_f32) d.flags |= ICD_GEMM_OUT_F32;
-        gemm_desc(d);
     }
     void free_act(Act& a) { release(a.p); release(a.aux); a.p = nullptr; a.aux = nullptr; }
     void free_aux(Act& a) { release(a.aux); a.aux = nullptr; }
@@ -309,7 +211,7 @@ struct Exec {
                    half_t* aux = nullptr, int ld_aux = 0) {
         if (!ok() || dry) return;
         const int C = x0.C + (x1 ? x1->C : 0);
-        ProfScope ps(true, st, ICD_PROF_GROUPNORM, 0.0, (split() ? 7.0 : 6.0) * B * (double)HW * C + 2.0 * B * (double)HW * (aux ? ld_aux : 0));
+        ProfScope ps(st, ICD_PROF_GROUPNORM, 0.0, (split() ? 7.0 : 6.0) * B * (double)HW * C + 2.0 * B * (double)HW * (aux ? ld_aux : 0));
         if (split())
             run(icd_groupnorm_carry(x0.p, x0.C, x0.aux, x1 ? x1->p : nullptr, x1 ? x1->C : 0, x1 ? x1->aux : nullptr, B, HW,
                                     u->cfg.norm_groups, g, b, eps, silu, out, aux, ld_aux, gn_ws, st));
@@ -320,7 +222,7 @@ struct Exec {
     half_t* expand(const void* carry, long long elems) {
         half_t* lo = alloc<half_t>(elems);
         if (ok() && !dry) {
-            ProfScope ps(true, st, ICD_PROF_MISC, 0.0, 3.0 * (double)elems);
+            ProfScope ps(st, ICD_PROF_MISC, 0.0, 3.0 * (double)elems);
             run(icd_carry_expand(carry, elems, lo, st));
         }
         return lo;
@@ -328,11 +230,12 @@ struct Exec {
     // LayerNorm statistics by a pass over the stream (2 B / element read) - only when the consuming GEMM does not compute them
     void ln_stats(const half_t* x, long long rows, int C, float* stats) {
         if (!ok() || dry || u->ln_inline) return;
-        ProfScope ps(true, st, ICD_PROF_LAYERNORM, 0.0, 2.0 * (double)rows * C);
+        ProfScope ps(st, ICD_PROF_LAYERNORM, 0.0, 2.0 * (double)rows * C);
         run(icd_layernorm_stats(x, rows, C, 1e-5f, stats, st));
     }
+    void silu(const half_t* x, long long elems, half_t* out) { if (ok() && !dry) run(icd_silu(x, elems, out, st)); }
 
-    // ---------------------------------------------------------------------------------------------- blocks
+    // ---------------------------------------------------------------------------------------------- ResnetBlock2D
     Act resnet(const std::string& p, const Act& x0, const Act* x1, int Hh, int Ww, int Cout) {
         const int HW = Hh * Ww, Cin = x0.C + (x1 ? x1->C : 0);
         const long long M = (long long)B * HW;
@@ -342,59 +245,52 @@ struct Exec {
         const int ld_sc = x0.C + (x1 ? 2 * x1->C : 0);
         half_t* sc_src = split_sc ? alloc<half_t>(M * ld_sc) : nullptr;
         groupnorm(x0, x1, HW, Wf(p + ".norm1.weight", Cin), Wf(p + ".norm1.bias", Cin), 1e-5f, 1, n1, sc_src, ld_sc);
-        half_t* h1 = alloc<half_t>(M * Cout);
-        void* h1c = split(ICD_SPLIT_GN) && split(ICD_SPLIT_CONV1) ? alloc_aux(M * Cout) : nullptr;     // conv1's output goes to norm2 with its carry
-        Act n1a{n1, Cin};
-        conv(n1a, nullptr, Hh, Ww, 3, 1, 0, Wh(p + ".conv1.weight", 9LL * Cin * Cout), Cout, Wf(p + ".conv1.bias", Cout),
-             temb_all + temb_off, u->temb_total, nullptr, h1, nullptr, h1c);
+        Act h1{alloc<half_t>(M * Cout), Cout};
+        h1.aux = split(ICD_SPLIT_GN) && split(ICD_SPLIT_CONV1) ? alloc_aux(M * Cout) : nullptr;     // conv1's output goes to norm2 with its carry
+        icd_gemm_desc c1 = conv(Act{n1, Cin}, nullptr, Hh, Ww, 3, 1, 0, Wh(p + ".conv1.weight", 9LL * Cin * Cout), Cout, h1.p);
+        c1.bias = Wf(p + ".conv1.bias", Cout);
+        c1.rowbias = temb_all + temb_off; c1.ld_rowbias = u->temb_total;
+        set_aux(c1, nullptr, h1.aux);
+        launch(c1);
         temb_off += Cout;
         release(n1);
         half_t* n2 = alloc<half_t>(M * Cout);
-        Act h1a{h1, Cout};
-        h1a.aux = h1c;
-        groupnorm(h1a, nullptr, HW, Wf(p + ".norm2.weight", Cout), Wf(p + ".norm2.bias", Cout), 1e-5f, 1, n2);
-        release(h1); release(h1c);
+        groupnorm(h1, nullptr, HW, Wf(p + ".norm2.weight", Cout), Wf(p + ".norm2.bias", Cout), 1e-5f, 1, n2);
+        free_act(h1);
         const int rm = u->resid_mode;
         const half_t* resid = x0.p;
         const void* resid_aux = rm ? x0.aux : nullptr;
         half_t* sc = nullptr;
         void* sc_aux = nullptr;
         if (Cin != Cout) {
-            if (rm == 1) {                           // the shortcut is only ever a residual: fp32 output, no fp16 copy
-                sc_aux = alloc<float>(M * Cout);
-                conv(x0, x1, Hh, Ww, 1, 1, 0, Wh(p + ".conv_shortcut.weight", (long long)Cin * Cout), Cout,
-                     Wf(p + ".conv_shortcut.bias", Cout), nullptr, 0, nullptr, sc_aux, nullptr, nullptr, true);
-            } else if (split_sc) {                   // [x0 | x1 | lo0 | lo1] against [W | W]: the shortcut of the values the stream holds
-                sc = alloc<half_t>(M * Cout);
-                sc_aux = alloc_aux(M * Cout);
-                Act s1{sc_src, ld_sc};
-                alg_k = Cin;
-                conv(x0, &s1, Hh, Ww, 1, 1, 0, Wh(p + ".conv_shortcut.weight2", 2LL * Cin * Cout), Cout,
-                     Wf(p + ".conv_shortcut.bias", Cout), nullptr, 0, nullptr, sc, nullptr, sc_aux);
-                resid = sc;
-            } else {                                 // fp16 (+ its error carry in mode 2)
-                sc = alloc<half_t>(M * Cout);
-                sc_aux = alloc_aux(M * Cout);
-                conv(x0, x1, Hh, Ww, 1, 1, 0, Wh(p + ".conv_shortcut.weight", (long long)Cin * Cout), Cout,
-                     Wf(p + ".conv_shortcut.bias", Cout), nullptr, 0, nullptr, sc, nullptr, sc_aux);
-                resid = sc;
-            }
+            // the shortcut conv: fp16 (+ its error carry in mode 2); mode 1: it is only ever a residual - fp32 output, no fp16 copy;
+            // split: [x0 | x1 | lo0 | lo1] against [W | W], the shortcut of the values the stream holds
+            if (rm != 1) resid = sc = alloc<half_t>(M * Cout);
+            sc_aux = alloc_aux(M * Cout);
+            const Act s1{sc_src, ld_sc};
+            icd_gemm_desc s = split_sc ? conv(x0, &s1, Hh, Ww, 1, 1, 0, Wh(p + ".conv_shortcut.weight2", 2LL * Cin * Cout), Cout, sc)
+                                       : conv(x0, x1, Hh, Ww, 1, 1, 0, Wh(p + ".conv_shortcut.weight", (long long)Cin * Cout), Cout, sc);
+            s.bias = Wf(p + ".conv_shortcut.bias", Cout);
+            if (rm == 1) { s.out = sc_aux; s.flags |= ICD_GEMM_OUT_F32; }
+            else set_aux(s, nullptr, sc_aux);
+            launch(s, split_sc ? Cin : 0);
             release(sc_src);
             resid_aux = sc_aux;
         }
-        half_t* out = alloc<half_t>(M * Cout);
-        void* out_aux = alloc_aux(M * Cout);
-        Act n2a{n2, Cout};
-        conv(n2a, nullptr, Hh, Ww, 3, 1, 0, Wh(p + ".conv2.weight", 9LL * Cout * Cout), Cout, Wf(p + ".conv2.bias", Cout),
-             nullptr, 0, (rm == 1 && resid_aux) ? nullptr : resid, out, resid_aux, out_aux);
+        Act o{alloc<half_t>(M * Cout), Cout};
+        o.aux = alloc_aux(M * Cout);
+        icd_gemm_desc c2 = conv(Act{n2, Cout}, nullptr, Hh, Ww, 3, 1, 0, Wh(p + ".conv2.weight", 9LL * Cout * Cout), Cout, o.p);
+        c2.bias = Wf(p + ".conv2.bias", Cout);
+        c2.resid = resid;
+        set_aux(c2, resid_aux, o.aux);
+        launch(c2);
         release(n2);
         release(sc);
         release(sc_aux);
-        Act o{out, Cout};
-        o.aux = out_aux;
         return o;
     }
 
+    // ---------------------------------------------------------------------------------------------- attention
     // Phase 0 of the plugin protocol for the next Attention module (module-execution order): does the controller want its
     // probabilities?  Asked BEFORE the query projection is enqueued, because a cross-attention layer that is not
     // materialised runs as the epilogue of that projection (icd_gemm xattn_*).
@@ -417,176 +313,272 @@ struct Exec {
         return a;
     }
 
-    // one attention module: q [B*Nq, ldq] (head h at col h*d), k [B*Nk, ldk], vt [B, C, ldv]; out [B*Nq, C]
+    // one Transformer2DModel's blocks: h [M, C] the residual stream (hx its fp32 twin / error carry), lnst the LayerNorm statistics of its
+    // rows, lnc = ICD_GEMM_LN_COMPUTE where the consuming GEMM computes them, place 0 down / 1 mid / 2 up
+    struct TBlock { half_t* h; void* hx; float* lnst; long long M; int C, HW, heads, lnc, place; };
+    // operands of one attention module: q [B*Nq, ldq] (head h at col h*d), k [B*Nk, ldk], vt [B, C, ldv] (sample stride vt_bs);
     // q_c / k_c: error carries of q / k (split mode, materialised layers only), or null
-    void attention(const AttnPlan& plan, bool is_cross, int place, const half_t* q, int ldq, const half_t* k, int ldk, const half_t* vt,
-                   int ldv, long long vt_bs, int heads, int Nq, int Nk, int d, half_t* out, int C, const void* q_c = nullptr,
-                   const void* k_c = nullptr) {
-        const int my_layer = plan.layer;
+    struct AttnOps { const half_t* q; int ldq; const half_t* k; int ldk; const half_t* vt; int ldv; long long vt_bs; const void* q_c; const void* k_c; };
+    // The packer (unet.pack_state_dict) folds d^-1/2 * log2(e) into every query projection: q.k already is the base-2
+    // exponent of the softmax.  The flash kernels take it as such (ICD_ATTN_Q_PRESCALED: no scale FMA per score, the running
+    // offset subtracted by the MFMA); the kernels with a `scale` argument get ln 2, i.e. scale * log2(e) == 1.
+    static constexpr float kScale = 0.69314718055994531f;
+
+    // flash attention of the first nb samples: out [nb*Nq, C]
+    void flash(const TBlock& t, const AttnOps& a, int nb, int Nk, half_t* out) {
+        if (!ok() || dry) return;
+        const int d = t.C / t.heads;
+        ProfScope ps(st, ICD_PROF_ATTN_FUSED, 4.0 * nb * t.heads * (double)t.HW * Nk * d, 0.0, t.HW, Nk, d, t.heads);
+        run(icd_attention_fused_ex(a.q, a.k, a.vt, out, nb, t.heads, t.HW, Nk, d, a.ldq, a.ldk, a.ldv, t.C, a.vt_bs, kScale,
+                                   ICD_ATTN_Q_PRESCALED | (u->attn_mode0 ? ICD_ATTN_TUNE_MODE0 : 0), st));
+    }
+    // one attention module over Nq = HW queries and Nk keys: out [B*Nq, C]
+    void attention(const TBlock& t, const AttnPlan& plan, bool is_cross, const AttnOps& a, int Nk, half_t* out) {
+        const int Nq = t.HW, heads = t.heads, C = t.C, d = C / heads;
         const long long ldp = (Nk + 7) / 8 * 8;
-        // The packer (unet.pack_state_dict) folds d^-1/2 * log2(e) into every query projection: q.k already is the base-2
-        // exponent of the softmax.  The flash kernels take it as such (ICD_ATTN_Q_PRESCALED: no scale FMA per score, the running
-        // offset subtracted by the MFMA); the kernels with a `scale` argument get ln 2, i.e. scale * log2(e) == 1.
-        const float scale = 0.69314718055994531f;
-        (void)d;
-        const bool mat = plan.mat;
-        void* probs = plan.probs;
         if (!ok()) return;
-        if (!mat) {
-            if (ok() && !dry) {
-                ProfScope ps(true, st, ICD_PROF_ATTN_FUSED, 4.0 * B * heads * (double)Nq * Nk * d, 0.0, Nq, Nk, d, heads);
-                run(icd_attention_fused_ex(q, k, vt, out, B, heads, Nq, Nk, d, ldq, ldk, ldv, C, vt_bs, scale,
-                                           ICD_ATTN_Q_PRESCALED | (u->attn_mode0 ? ICD_ATTN_TUNE_MODE0 : 0), st));
-            }
-            return;
-        }
+        if (!plan.mat) { flash(t, a, B, Nk, out); return; }
         // materialised path (utils/p2p.py:335-338): P = softmax(scale q.k^T) as fp16 in ONE pass (icd_attention_probs: no
         // fp32 score tensor) -> hook (the controller edits / keeps P) -> P.V.  plan.half (round 5): the controller works on the second half
         // of the batch only (utils/p2p.py:153-155: attn[h // 2:] of a [uncond; cond] batch) - the first half runs the fused kernel, P is
         // written and read back for the conditional samples alone
         const int b0 = plan.half ? B / 2 : 0, Bm = B - b0;
-        if (b0 && !dry) {
-            ProfScope ps(true, st, ICD_PROF_ATTN_FUSED, 4.0 * b0 * heads * (double)Nq * Nk * d, 0.0, Nq, Nk, d, heads);
-            run(icd_attention_fused_ex(q, k, vt, out, b0, heads, Nq, Nk, d, ldq, ldk, ldv, C, vt_bs, scale,
-                                       ICD_ATTN_Q_PRESCALED | (u->attn_mode0 ? ICD_ATTN_TUNE_MODE0 : 0), st));
-        }
-        const long long qo = (long long)b0 * Nq * ldq, ko = (long long)b0 * Nk * ldk;
-        const half_t* qm = q + qo;
-        const half_t* km = k + ko;
-        const void* qcm = q_c ? (const unsigned char*)q_c + qo : nullptr;
-        const void* kcm = k_c ? (const unsigned char*)k_c + ko : nullptr;
+        if (b0) flash(t, a, b0, Nk, out);
+        const long long qo = (long long)b0 * Nq * a.ldq, ko = (long long)b0 * Nk * a.ldk;
+        const void* qcm = a.q_c ? (const unsigned char*)a.q_c + qo : nullptr;
+        const void* kcm = a.k_c ? (const unsigned char*)a.k_c + ko : nullptr;
         const long long per_b = (long long)heads * Nq * ldp;            // elements of P per sample
+        void* probs = plan.probs;
         if (!dry && ok()) {
-            ProfScope ps(true, st, ICD_PROF_SOFTMAX, 2.0 * Bm * heads * (double)Nq * Nk * d, (double)Bm * per_b * 2.0, Nq, Nk, d,
-                         heads | (q_c ? 256 : 0) | (plan.has_epi ? 512 : 0));
-            run(icd_attention_probs_ex(qm, qcm, km, kcm, probs, Bm, heads, Nq, Nk, d, ldq, ldk, (int)ldp, scale, plan.has_epi ? &plan.epi : nullptr, st));
+            ProfScope ps(st, ICD_PROF_SOFTMAX, 2.0 * Bm * heads * (double)Nq * Nk * d, (double)Bm * per_b * 2.0, Nq, Nk, d,
+                         heads | (a.q_c ? 256 : 0) | (plan.has_epi ? 512 : 0));
+            run(icd_attention_probs_ex(a.q + qo, qcm, a.k + ko, kcm, probs, Bm, heads, Nq, Nk, d, a.ldq, a.ldk, (int)ldp, kScale,
+                                       plan.has_epi ? &plan.epi : nullptr, st));
         }
         if (!dry && ok()) {
-            const int r = io->hook(io->hook_user, ICD_HOOK_PROBS, my_layer, is_cross, place, (long long)Bm * heads, Nq, Nk, ldp, &probs);
-            if (r < 0) { icd_set_error("attention hook (probs) failed at layer %d", my_layer); status = ICD_ERR_HOOK; return; }
+            const int r = io->hook(io->hook_user, ICD_HOOK_PROBS, plan.layer, is_cross, t.place, (long long)Bm * heads, Nq, Nk, ldp, &probs);
+            if (r < 0) { icd_set_error("attention hook (probs) failed at layer %d", plan.layer); status = ICD_ERR_HOOK; return; }
         }
-        icd_gemm_desc g; memset(&g, 0, sizeof(g));
-        g.a0 = probs; g.w = vt + (long long)b0 * vt_bs; g.out = out + (long long)b0 * Nq * C;
-        g.M = Nq; g.N = d; g.K = (int)ldp; g.Nw = d; g.lda = (int)ldp; g.ldw = ldv; g.ldo = C;
-        g.mode = 0; g.batch = Bm * heads; g.zdiv = heads;
-        g.a_bs0 = per_b; g.a_bs1 = (long long)Nq * ldp; g.w_bs0 = vt_bs; g.w_bs1 = (long long)d * ldv;
+        icd_gemm_desc g = dense(probs, (int)ldp, Nq, (int)ldp, a.vt + (long long)b0 * a.vt_bs, d, out + (long long)b0 * Nq * C, C);
+        g.ldw = a.ldv; g.batch = Bm * heads; g.zdiv = heads;
+        g.a_bs0 = per_b; g.a_bs1 = (long long)Nq * ldp; g.w_bs0 = a.vt_bs; g.w_bs1 = (long long)d * a.ldv;
         g.o_bs0 = (long long)Nq * C; g.o_bs1 = d;
-        g.alpha = 1.f;
-        gemm_desc(g);
+        launch(g);
+    }
+
+    // h <- h + a W^T + bias in place on the transformer's residual stream: `name` is attn1.to_out.0, attn2.to_out.0 or ff.net.2
+    void add_to_stream(const TBlock& t, const half_t* a, int K, const std::string& name) {
+        icd_gemm_desc d = dense(a, K, t.M, K, Wh(name + ".weight", (long long)t.C * K), t.C, t.h, t.C);
+        d.bias = Wf(name + ".bias", t.C);
+        d.resid = t.h; d.ldr = t.C;
+        set_aux(d, t.hx, t.hx);
+        launch(d);
+    }
+    // a projection behind a LayerNorm that is never materialised: out [M, N] (ldo) = LN(h) W^T; the caller sets bias, flags and the rest
+    icd_gemm_desc ln_dense(const TBlock& t, const std::string& name, int N, void* out, int ldo) {
+        icd_gemm_desc d = dense(t.h, t.C, t.M, t.C, Wh(name + ".weight", (long long)N * t.C), N, out, ldo);
+        d.ln_stats = t.lnst; d.ln_colsum = Wf(name + ".lnsum", N);
+        return d;
+    }
+
+    // returns the attention output ao [M, C], which cross_attention() reuses and releases
+    half_t* self_attention(const TBlock& t, const std::string& b) {
+        const int C = t.C, ldv = (t.HW + 7) / 8 * 8;
+        ln_stats(t.h, t.M, C, t.lnst);
+        // (the controller is asked before the projection is enqueued: a layer whose probabilities it keeps gets q and k with their
+        //  error carry in split mode - through the general epilogue and a statistics launch, only on such layers)
+        const AttnPlan plan = attn_query(false, t.place, t.heads, t.HW, t.HW);
+        half_t* qk = alloc<half_t>(t.M * 2 * C);
+        void* qk_c = (plan.mat && split(ICD_SPLIT_QK)) ? alloc_aux(t.M * 2 * C) : nullptr;
+        icd_gemm_desc pq = ln_dense(t, b + ".attn1.to_qk", 2 * C, qk, 2 * C);
+        pq.bias = Wf(b + ".attn1.to_qk.lnbias", 2 * C);
+        pq.flags = qk_c ? (t.lnc | ICD_GEMM_TUNE_NO_LN_INLINE) : t.lnc;
+        set_aux(pq, nullptr, qk_c);
+        launch(pq);
+        half_t* vt = alloc<half_t>((long long)B * C * ldv);
+        icd_gemm_desc pv = ln_dense(t, b + ".attn1.to_v", C, vt, ldv);      // (W_v beta) rides in to_out's bias
+        pv.flags = ICD_GEMM_OUT_TRANS; pv.rows_per_sample = t.HW;
+        launch(pv);
+        half_t* ao = alloc<half_t>(t.M * C);
+        attention(t, plan, false, AttnOps{qk, 2 * C, qk + C, 2 * C, vt, ldv, (long long)C * ldv, qk_c, qk_c ? (const unsigned char*)qk_c + C : nullptr},
+                  t.HW, ao);
+        release(qk); release(vt); release(qk_c);
+        add_to_stream(t, ao, C, b + ".attn1.to_out.0");
+        return ao;
+    }
+
+    // LN2 -> to_q -> cross-attention as ONE launch (icd_gemm xattn_*): where the kernel is eligible (a layer whose probabilities nobody
+    // keeps, heads of 64 columns) and, under the default rule, where it measured faster - see icd_unet::xattn_mode
+    bool xattn_fusable(const TBlock& t, bool materialised) const {
+        const int C = t.C;
+        const long long xa_blocks = (t.M / 256) * (C / 256), xa_b192 = (long long)B * ((t.HW + 191) / 192) * (C / 256);
+        const bool xa_auto = C % 256 == 0 && xa_blocks >= 64 && xa_b192 <= 512;
+        return !materialised && C / t.heads == 64 && C % 128 == 0 && t.HW % 256 == 0 && nctx <= 96 &&
+               (u->xattn_mode == 1 || (u->xattn_mode == 2 && xa_auto));
+    }
+    void cross_attention(const TBlock& t, const std::string& b, half_t* ao) {
+        const int C = t.C, ldv = (nctx + 7) / 8 * 8;
+        ln_stats(t.h, t.M, C, t.lnst);
+        // K and V^T of this layer are column / row slices of the per-forward batched projections
+        const half_t* kx = k_all + kv_off;
+        const half_t* vx = vt_all + (long long)kv_off * ldv;
+        const long long vx_bs = (long long)u->kv_total * ldv;
+        const AttnPlan plan = attn_query(true, t.place, t.heads, t.HW, nctx);
+        const bool fused = xattn_fusable(t, plan.mat);
+        half_t* q2 = fused ? nullptr : alloc<half_t>(t.M * C);
+        void* q2_c = (!fused && plan.mat && split(ICD_SPLIT_QK)) ? alloc_aux(t.M * C) : nullptr;
+        icd_gemm_desc pq = ln_dense(t, b + ".attn2.to_q", C, fused ? ao : q2, C);
+        pq.bias = Wf(b + ".attn2.to_q.lnbias", C);
+        if (fused) {
+            // the north-star kernel: LN2 -> to_q -> softmax(q K^T / 8) V in ONE launch, q stays in the accumulators
+            pq.flags = t.lnc; pq.rows_per_sample = t.HW;
+            pq.xattn_k = kx; pq.xattn_vt = vx; pq.xattn_nk = nctx; pq.xattn_ldk = u->kv_total; pq.xattn_ldvt = ldv;
+            pq.xattn_vt_bs = vx_bs; pq.xattn_scale = kScale; pq.tune_xattn_tile = u->xattn_tile;      // q is prescaled (see kScale)
+            if (ok() && !dry) {      // (its own family; no split-K scratch and no gemm_tune bits: not a launch() launch)
+                ProfScope ps(st, ICD_PROF_XATTN, 2.0 * t.M * (double)C * C + 4.0 * t.M * (double)nctx * C, 0.0, (int)t.M, C, C, t.heads);
+                ps.plan(pq);
+                run(icd_gemm(&pq, st));
+            }
+        } else {
+            pq.flags = q2_c ? (t.lnc | ICD_GEMM_TUNE_NO_LN_INLINE) : t.lnc;
+            set_aux(pq, nullptr, q2_c);
+            launch(pq);
+            attention(t, plan, true, AttnOps{q2, C, kx, u->kv_total, vx, ldv, vx_bs, q2_c, (q2_c && k_all_c) ? k_all_c + kv_off : nullptr}, nctx, ao);
+            release(q2); release(q2_c);
+        }
+        kv_off += C;
+        add_to_stream(t, ao, C, b + ".attn2.to_out.0");
+        release(ao);
+    }
+
+    // the GEGLU projection and the output projection as ONE launch (icd_ffn_geglu) - the rule and its measurements: icd_unet::ffn_mode
+    bool ffn_fusable(const TBlock& t) const {
+        return t.C == 320 && (u->ffn_mode == 1 || (u->ffn_mode == 2 && t.M >= 65536 && u->gemm_tune == 0));
+    }
+    void feed_forward(const TBlock& t, const std::string& b) {
+        const int C = t.C;
+        ln_stats(t.h, t.M, C, t.lnst);
+        if (!ffn_fusable(t)) {
+            half_t* ff = alloc<half_t>(t.M * 4 * C);
+            icd_gemm_desc p = ln_dense(t, b + ".ff.net.0.proj", 8 * C, ff, 4 * C);
+            p.bias = Wf(b + ".ff.net.0.proj.bias", 8 * C);
+            p.flags = ICD_GEMM_GEGLU | t.lnc;
+            launch(p);
+            add_to_stream(t, ff, 4 * C, b + ".ff.net.2");
+            release(ff);
+            return;
+        }
+        // h <- h + FF(LN(h)) in place, the hidden tensor stays in the accumulators (no arena buffer for it)
+        icd_ffn_desc f; memset(&f, 0, sizeof(f));
+        f.x = t.h; f.out = t.h; f.M = (int)t.M; f.C = C; f.hidden = 4 * C; f.ldx = C; f.ldw1 = C; f.ldw2 = 4 * C; f.ldo = C; f.ldr = C;
+        f.w1 = Wh(b + ".ff.net.0.proj.weight", 8LL * C * C); f.b1 = Wf(b + ".ff.net.0.proj.bias", 8 * C);
+        f.ln_colsum = Wf(b + ".ff.net.0.proj.lnsum", 8 * C); f.ln_stats = t.lnst; f.flags = t.lnc;
+        f.w2 = Wh(b + ".ff.net.2.weight", 4LL * C * C); f.b2 = Wf(b + ".ff.net.2.bias", C);
+        if (u->resid_mode == 1) { f.resid = t.hx; f.flags |= ICD_GEMM_RESID_F32; f.out_f32 = (float*)t.hx; }     // (the fp32 twin is the residual)
+        else { f.resid = t.h; f.resid_carry = t.hx; f.out_carry = t.hx; }
+        if (!ok() || dry) return;
+        // family gemm_dense with the algorithmic flops of the two projections it replaces; no tile record (not a planner launch)
+        ProfScope ps(st, ICD_PROF_GEMM_DENSE, 2.0 * t.M * (double)C * (8.0 * C + 4.0 * C), 0.0, (int)t.M, C, 4 * C, ICD_GEMM_GEGLU);
+        run(icd_ffn_geglu(&f, st));
     }
 
     Act transformer(const std::string& p, const Act& x, int Hh, int Ww, int depth, int heads, int place) {
-        const int HW = Hh * Ww, C = x.C, d = C / heads, X = u->cfg.cross_dim;
+        const int HW = Hh * Ww, C = x.C;
         const long long M = (long long)B * HW;
-        const int ldv_self = (HW + 7) / 8 * 8, ldv_cross = (nctx + 7) / 8 * 8;
         half_t* n = alloc<half_t>(M * C);
         groupnorm(x, nullptr, HW, Wf(p + ".norm.weight", C), Wf(p + ".norm.bias", C), 1e-6f, 0, n);
-        half_t* h = alloc<half_t>(M * C);
-        void* hx = alloc_aux(M * C);                 // fp32 twin / error carry of the transformer blocks' residual stream
-        const bool tw = u->resid_mode == 1;          // fp32 twin: the twin IS the residual operand (no fp16 resid beside it)
-        linear(n, C, (int)M, C, Wh(p + ".proj_in.weight", (long long)C * C), C, Wf(p + ".proj_in.bias", C), nullptr, 0, h, C, 0, 0,
-               nullptr, nullptr, nullptr, hx);
         // the first GEMM behind each LayerNorm computes the statistics of its input rows itself (from its MFMA operand fragments
         // where the tile kernel can, see icd_gemm) and leaves them in lnst for a second consumer (to_v after to_qk)
-        const int lnc = u->ln_inline ? ICD_GEMM_LN_COMPUTE : 0;
+        TBlock t{alloc<half_t>(M * C), nullptr, nullptr, M, C, HW, heads, u->ln_inline ? ICD_GEMM_LN_COMPUTE : 0, place};
+        t.hx = alloc_aux(M * C);                     // fp32 twin / error carry of the transformer blocks' residual stream
+        icd_gemm_desc pin = dense(n, C, M, C, Wh(p + ".proj_in.weight", (long long)C * C), C, t.h, C);
+        pin.bias = Wf(p + ".proj_in.bias", C);
+        set_aux(pin, nullptr, t.hx);
+        launch(pin);
         release(n);
         // LayerNorm is never materialised: per-row (mean, rstd) from a statistics pass over the residual stream, gamma
         // folded into the consuming projection's weights at load time (unet.py), the rank-1 correction in its epilogue.
-        float* lnst = alloc<float>(M * 2);
+        t.lnst = alloc<float>(M * 2);
         for (int kb = 0; kb < depth && ok(); ++kb) {
             const std::string b = p + ".transformer_blocks." + std::to_string(kb);
-            // ---- self attention ----
-            ln_stats(h, M, C, lnst);
-            // (the controller is asked before the projection is enqueued: a layer whose probabilities it keeps gets q and k with their
-            //  error carry in split mode - through the general epilogue and a statistics launch, only on such layers)
-            const AttnPlan self_plan = attn_query(false, place, heads, HW, HW);
-            half_t* qk = alloc<half_t>(M * 2 * C);
-            void* qk_c = (self_plan.mat && split(ICD_SPLIT_QK)) ? alloc_aux(M * 2 * C) : nullptr;
-            linear(h, C, (int)M, C, Wh(b + ".attn1.to_qk.weight", 2LL * C * C), 2 * C, Wf(b + ".attn1.to_qk.lnbias", 2 * C), nullptr, 0, qk,
-                   2 * C, qk_c ? (lnc | ICD_GEMM_TUNE_NO_LN_INLINE) : lnc, 0, lnst, Wf(b + ".attn1.to_qk.lnsum", 2 * C), nullptr, qk_c);
-            half_t* vt = alloc<half_t>((long long)B * C * ldv_self);
-            linear(h, C, (int)M, C, Wh(b + ".attn1.to_v.weight", (long long)C * C), C, nullptr, nullptr, 0, vt, ldv_self,
-                   ICD_GEMM_OUT_TRANS, HW, lnst, Wf(b + ".attn1.to_v.lnsum", C));      // (W_v beta) rides in to_out's bias
-            half_t* ao = alloc<half_t>(M * C);
-            attention(self_plan, false, place, qk, 2 * C, qk + C, 2 * C, vt, ldv_self, (long long)C * ldv_self, heads, HW, HW, d, ao, C,
-                      qk_c, qk_c ? (const unsigned char*)qk_c + C : nullptr);
-            release(qk); release(vt); release(qk_c);
-            linear(ao, C, (int)M, C, Wh(b + ".attn1.to_out.0.weight", (long long)C * C), C, Wf(b + ".attn1.to_out.0.bias", C), tw ? nullptr : h, C,
-                   h, C, 0, 0, nullptr, nullptr, hx, hx);
-            // ---- cross attention ----
-            ln_stats(h, M, C, lnst);
-            // K and V^T of this layer are column / row slices of the per-forward batched projections
-            const half_t* kx = k_all + kv_off;
-            const half_t* vx = vt_all + (long long)kv_off * ldv_cross;
-            const long long vx_bs = (long long)u->kv_total * ldv_cross;
-            const AttnPlan cross_plan = attn_query(true, place, heads, HW, nctx);
-            const half_t* wq = Wh(b + ".attn2.to_q.weight", (long long)C * C);
-            const float* bq = Wf(b + ".attn2.to_q.lnbias", C);
-            const float* sq = Wf(b + ".attn2.to_q.lnsum", C);
-            const long long xa_blocks = (M / 256) * (C / 256), xa_b192 = (long long)B * ((HW + 191) / 192) * (C / 256);
-            const bool xa_auto = C % 256 == 0 && xa_blocks >= 64 && xa_b192 <= 512;
-            if (!cross_plan.mat && d == 64 && C % 128 == 0 && HW % 256 == 0 && nctx <= 96 && (u->xattn_mode == 1 || (u->xattn_mode == 2 && xa_auto))) {
-                // the north-star kernel: LN2 -> to_q -> softmax(q K^T / 8) V in ONE launch, q stays in the accumulators
-                if (ok() && !dry) {
-                    icd_gemm_desc g; memset(&g, 0, sizeof(g));
-                    g.a0 = h; g.w = wq; g.bias = bq; g.out = ao;
-                    g.M = (int)M; g.N = C; g.K = C; g.Nw = C; g.lda = C; g.ldw = C; g.ldo = C;
-                    g.rows_per_sample = HW; g.mode = 0; g.batch = 1; g.zdiv = 1; g.alpha = 1.f;
-                    g.ln_stats = lnst; g.ln_colsum = sq; g.flags = lnc;
-                    g.xattn_k = kx; g.xattn_vt = vx; g.xattn_nk = nctx; g.xattn_ldk = u->kv_total; g.xattn_ldvt = ldv_cross;
-                    g.xattn_vt_bs = vx_bs; g.xattn_scale = 0.69314718055994531f; g.tune_xattn_tile = u->xattn_tile;   // q is prescaled (see attention())
-                    ProfScope ps(true, st, ICD_PROF_XATTN, 2.0 * M * (double)C * C + 4.0 * M * (double)nctx * C, 0.0, (int)M, C, C, heads);
-                    ps.plan(g);
-                    run(icd_gemm(&g, st));
-                }
-            } else {
-                half_t* q2 = alloc<half_t>(M * C);
-                void* q2_c = (cross_plan.mat && split(ICD_SPLIT_QK)) ? alloc_aux(M * C) : nullptr;
-                linear(h, C, (int)M, C, wq, C, bq, nullptr, 0, q2, C, q2_c ? (lnc | ICD_GEMM_TUNE_NO_LN_INLINE) : lnc, 0, lnst, sq, nullptr, q2_c);
-                attention(cross_plan, true, place, q2, C, kx, u->kv_total, vx, ldv_cross, vx_bs, heads, HW, nctx, d, ao, C, q2_c,
-                          (q2_c && k_all_c) ? k_all_c + kv_off : nullptr);
-                release(q2); release(q2_c);
-            }
-            kv_off += C;
-            linear(ao, C, (int)M, C, Wh(b + ".attn2.to_out.0.weight", (long long)C * C), C, Wf(b + ".attn2.to_out.0.bias", C), tw ? nullptr : h, C,
-                   h, C, 0, 0, nullptr, nullptr, hx, hx);
-            release(ao);
-            // ---- GEGLU feed-forward ----
-            ln_stats(h, M, C, lnst);
-            if (C == 320 && (u->ffn_mode == 1 || (u->ffn_mode == 2 && M >= 65536 && u->gemm_tune == 0))) {
-                // one launch, the hidden tensor stays in the accumulators (no arena buffer for it)
-                ffn_fused(h, (int)M, C, Wh(b + ".ff.net.0.proj.weight", 8LL * C * C), Wf(b + ".ff.net.0.proj.bias", 8 * C),
-                          Wf(b + ".ff.net.0.proj.lnsum", 8 * C), lnst, lnc, Wh(b + ".ff.net.2.weight", 4LL * C * C), Wf(b + ".ff.net.2.bias", C),
-                          tw ? nullptr : h, hx);
-            } else {
-                half_t* ff = alloc<half_t>(M * 4 * C);
-                linear(h, C, (int)M, C, Wh(b + ".ff.net.0.proj.weight", 8LL * C * C), 8 * C, Wf(b + ".ff.net.0.proj.bias", 8 * C), nullptr, 0,
-                       ff, 4 * C, ICD_GEMM_GEGLU | lnc, 0, lnst, Wf(b + ".ff.net.0.proj.lnsum", 8 * C));
-                linear(ff, 4 * C, (int)M, 4 * C, Wh(b + ".ff.net.2.weight", 4LL * C * C), C, Wf(b + ".ff.net.2.bias", C), tw ? nullptr : h, C, h, C,
-                       0, 0, nullptr, nullptr, hx, hx);
-                release(ff);
-            }
+            cross_attention(t, b, self_attention(t, b));
+            feed_forward(t, b);
         }
-        release(lnst);
-        half_t* out = alloc<half_t>(M * C);
-        void* out_aux = alloc_aux(M * C);
+        release(t.lnst);
+        Act o{alloc<half_t>(M * C), C};
+        o.aux = alloc_aux(M * C);
         if (split(ICD_SPLIT_PROJ_OUT)) {             // proj_out over [h | lo] against [W | W] (a two-source 1x1 conv)
-            half_t* lo = expand(hx, M * C);
-            release(hx);
-            Act ha{h, C}, la{lo, C};
-            alg_k = C;
-            conv(ha, &la, Hh, Ww, 1, 1, 0, Wh(p + ".proj_out.weight2", 2LL * C * C), C, Wf(p + ".proj_out.bias", C), nullptr, 0, x.p, out,
-                 x.aux, out_aux);
+            half_t* lo = expand(t.hx, M * C);
+            release(t.hx);
+            const Act la{lo, C};
+            icd_gemm_desc d = conv(Act{t.h, C}, &la, Hh, Ww, 1, 1, 0, Wh(p + ".proj_out.weight2", 2LL * C * C), C, o.p);
+            d.bias = Wf(p + ".proj_out.bias", C);
+            d.resid = x.p;
+            set_aux(d, x.aux, o.aux);
+            launch(d, C);
             release(lo);
         } else {
-            release(hx);                             // (proj_out reads the fp16 copy of the stream as its operand)
-            linear(h, C, (int)M, C, Wh(p + ".proj_out.weight", (long long)C * C), C, Wf(p + ".proj_out.bias", C), (tw && x.aux) ? nullptr : x.p, C, out, C,
-                   0, 0, nullptr, nullptr, x.aux, out_aux);
+            release(t.hx);                           // (proj_out reads the fp16 copy of the stream as its operand)
+            icd_gemm_desc d = dense(t.h, C, M, C, Wh(p + ".proj_out.weight", (long long)C * C), C, o.p, C);
+            d.bias = Wf(p + ".proj_out.bias", C);
+            d.resid = x.p; d.ldr = C;
+            set_aux(d, x.aux, o.aux);
+            launch(d);
         }
-        release(h);
-        Act o{out, C};
-        o.aux = out_aux;
+        release(t.h);
         return o;
+    }
+
+    // ---------------------------------------------------------------------------------------------- time embedding
+    // Both forms leave temb_all [B, temb_total], the time projections of every resnet in execution order, in fp16.
+    // Timesteps -> (+cond_proj) -> Linear -> SiLU -> Linear (+ SDXL add_embedding), in fp16
+    int time_embedding_fp16() {
+        const icd_unet_config& c = u->cfg;
+        const int ch0 = c.block_out_channels[0], temb = ch0 * 4;
+        auto lin = [&](const half_t* a, int K, const std::string& name, int N, half_t* out, const half_t* resid = nullptr) {
+            icd_gemm_desc d = dense(a, K, B, K, Wh(name + ".weight", (long long)N * K), N, out, N);
+            d.bias = Wf(name + ".bias", N);
+            d.resid = resid; d.ldr = resid ? N : 0;
+            launch(d);
+        };
+        half_t* tsin = alloc<half_t>((long long)B * ch0);
+        if (ok() && !dry) run(icd_sinusoid(io->timesteps, B, ch0, 0, tsin, st));
+        half_t* tin = tsin;
+        if (c.time_cond_proj_dim > 0 && (dry ? true : io->timestep_cond != nullptr)) {
+            tin = alloc<half_t>((long long)B * ch0);
+            icd_gemm_desc d = dense(io->timestep_cond, c.time_cond_proj_dim, B, c.time_cond_proj_dim,
+                                    Wh("time_embedding.cond_proj.weight", (long long)ch0 * c.time_cond_proj_dim), ch0, tin, ch0);
+            d.resid = tsin; d.ldr = ch0;
+            launch(d);
+        }
+        half_t* e1 = alloc<half_t>((long long)B * temb);
+        lin(tin, ch0, "time_embedding.linear_1", temb, e1);
+        silu(e1, (long long)B * temb, e1);
+        half_t* emb = alloc<half_t>((long long)B * temb);
+        lin(e1, temb, "time_embedding.linear_2", temb, emb);
+        if (c.add_in_dim > 0) {
+            const int tdim = c.addition_time_embed_dim, pooled = c.add_in_dim - 6 * tdim;
+            half_t* tid = alloc<half_t>((long long)B * 6 * tdim);
+            if (ok() && !dry) {
+                if (!io->time_ids || !io->text_embeds) { icd_set_error("SDXL forward needs text_embeds and time_ids"); return ICD_ERR_INVALID_ARG; }
+                run(icd_sinusoid(io->time_ids, B * 6, tdim, 0, tid, st));
+            }
+            half_t* a1 = alloc<half_t>((long long)B * temb);
+            // Linear over cat([text_embeds, time_embeds]) without materialising the concat: 1x1 "conv" with two sources
+            const Act s1{tid, 6 * tdim};
+            icd_gemm_desc d = conv(Act{(half_t*)io->text_embeds, pooled}, &s1, 1, 1, 1, 1, 0,
+                                   Wh("add_embedding.linear_1.weight", (long long)temb * c.add_in_dim), temb, a1);
+            d.bias = Wf("add_embedding.linear_1.bias", temb);
+            launch(d);
+            silu(a1, (long long)B * temb, a1);
+            lin(a1, temb, "add_embedding.linear_2", temb, emb, emb);
+            release(a1); release(tid);
+        }
+        silu(emb, (long long)B * temb, e1);                               // e1 := SiLU(emb), shared by every resnet
+        temb_all = alloc<half_t>((long long)B * u->temb_total);
+        lin(e1, temb, "time_emb_proj_cat", u->temb_total, temb_all);
+        release(e1); release(emb); if (tin != tsin) release(tin); release(tsin);
+        return ICD_OK;
     }
 
     // The time-embedding path in fp32 precision (ICD_SPLIT_TEMB): fp32 sinusoids, every Linear over the split operand [hi | lo] of its fp32
@@ -601,21 +593,29 @@ struct Exec {
         const icd_unet_config& c = u->cfg;
         const int ch0 = c.block_out_channels[0], temb = ch0 * 4;
         const int F32 = ICD_GEMM_OUT_F32, R32 = ICD_GEMM_RESID_F32;
+        // out [B, N] = [hi | lo](s) @ [W | W]^T + bias (+ out, when `accumulate`), in fp32 unless flags say otherwise
+        auto lin2 = [&](const half_t* s, int K, const std::string& name, int N, void* out, int flags, bool accumulate = false) {
+            icd_gemm_desc d = dense(s, 2 * K, B, 2 * K, Wh(name + ".weight2", 2LL * N * K), N, out, N);
+            d.bias = Wf(name + ".bias", N);
+            d.flags = flags;
+            if (accumulate) { d.resid = out; d.ldr = N; }
+            launch(d);
+        };
         float* tin = alloc<float>((long long)B * ch0);
         if (ok() && !dry) run(icd_sinusoid_f32(io->timesteps, B, ch0, 0, tin, st));
-        if (c.time_cond_proj_dim > 0 && (dry ? true : io->timestep_cond != nullptr))      // + cond_proj(w) (an fp16 input: exact operand)
-            linear((const half_t*)io->timestep_cond, c.time_cond_proj_dim, B, c.time_cond_proj_dim,
-                   Wh("time_embedding.cond_proj.weight", (long long)ch0 * c.time_cond_proj_dim), ch0, nullptr, (const half_t*)tin, ch0,
-                   (half_t*)tin, ch0, F32 | R32);
+        if (c.time_cond_proj_dim > 0 && (dry ? true : io->timestep_cond != nullptr)) {     // + cond_proj(w) (an fp16 input: exact operand)
+            icd_gemm_desc d = dense(io->timestep_cond, c.time_cond_proj_dim, B, c.time_cond_proj_dim,
+                                    Wh("time_embedding.cond_proj.weight", (long long)ch0 * c.time_cond_proj_dim), ch0, tin, ch0);
+            d.resid = tin; d.ldr = ch0; d.flags = F32 | R32;
+            launch(d);
+        }
         half_t* s = split2(tin, B, ch0, 0);
         float* e1 = alloc<float>((long long)B * temb);
-        linear(s, 2 * ch0, B, 2 * ch0, Wh("time_embedding.linear_1.weight2", 2LL * temb * ch0), temb, Wf("time_embedding.linear_1.bias", temb),
-               nullptr, 0, (half_t*)e1, temb, F32);
+        lin2(s, ch0, "time_embedding.linear_1", temb, e1, F32);
         release(s); release(tin);
         s = split2(e1, B, temb, 1);
         float* emb = alloc<float>((long long)B * temb);
-        linear(s, 2 * temb, B, 2 * temb, Wh("time_embedding.linear_2.weight2", 2LL * temb * temb), temb, Wf("time_embedding.linear_2.bias", temb),
-               nullptr, 0, (half_t*)emb, temb, F32);
+        lin2(s, temb, "time_embedding.linear_2", temb, emb, F32);
         release(s);
         if (c.add_in_dim > 0) {
             const int tdim = c.addition_time_embed_dim, pooled = c.add_in_dim - 6 * tdim;
@@ -625,169 +625,187 @@ struct Exec {
             half_t* st2 = split2(tid, B, 6 * tdim, 0);
             release(tid);
             // Linear over cat([text_embeds (fp16 input: exact), hi(time_embeds), lo(time_embeds)]) against [W_text | W_time | W_time]
-            Act s0{(half_t*)io->text_embeds, pooled}, s1{st2, 12 * tdim};
-            conv(s0, &s1, 1, 1, 1, 1, 0, Wh("add_embedding.linear_1.weight2", (long long)temb * (pooled + 12 * tdim)), temb,
-                 Wf("add_embedding.linear_1.bias", temb), nullptr, 0, nullptr, e1, nullptr, nullptr, true);
+            const Act s1{st2, 12 * tdim};
+            icd_gemm_desc d = conv(Act{(half_t*)io->text_embeds, pooled}, &s1, 1, 1, 1, 1, 0,
+                                   Wh("add_embedding.linear_1.weight2", (long long)temb * (pooled + 12 * tdim)), temb, e1);
+            d.bias = Wf("add_embedding.linear_1.bias", temb);
+            d.flags = F32;
+            launch(d);
             release(st2);
             s = split2(e1, B, temb, 1);
-            linear(s, 2 * temb, B, 2 * temb, Wh("add_embedding.linear_2.weight2", 2LL * temb * temb), temb, Wf("add_embedding.linear_2.bias", temb),
-                   (const half_t*)emb, temb, (half_t*)emb, temb, F32 | R32);
+            lin2(s, temb, "add_embedding.linear_2", temb, emb, F32 | R32, true);
             release(s);
         }
         release(e1);
         s = split2(emb, B, temb, 1);                                  // SiLU(emb), shared by every resnet
         release(emb);
         temb_all = alloc<half_t>((long long)B * u->temb_total);
-        linear(s, 2 * temb, B, 2 * temb, Wh("time_emb_proj_cat.weight2", 2LL * u->temb_total * temb), u->temb_total,
-               Wf("time_emb_proj_cat.bias", u->temb_total), nullptr, 0, temb_all, u->temb_total);
+        lin2(s, temb, "time_emb_proj_cat", u->temb_total, temb_all, 0);
         release(s);
         return status;
     }
 
+    // ---------------------------------------------------------------------------------------------- the blocks of forward()
+    // every cross-attention K / V projection depends on the context only: two GEMMs for the whole forward, or none when the caller's
+    // cache of them (icd_unet_io.kv_cache) is valid
+    int context_kv() {
+        const int X = u->cfg.cross_dim, Mc = B * nctx, ldvc = (nctx + 7) / 8 * 8, N = u->kv_total;
+        const long long k_elems = (long long)Mc * N, v_elems = (long long)B * N * ldvc;
+        bool have = false;
+        if (!dry && io->kv_cache) {
+            if (io->kv_cache_bytes < (k_elems + v_elems) * 2 + k_elems) {
+                icd_set_error("icd_unet_forward: kv_cache too small (%lld bytes given); query icd_unet_kv_cache_bytes", (long long)io->kv_cache_bytes);
+                return ICD_ERR_WORKSPACE;
+            }
+            k_all = (half_t*)io->kv_cache; vt_all = k_all + k_elems; kv_external = true;
+            if (split(ICD_SPLIT_QK)) k_all_c = (unsigned char*)(vt_all + v_elems);       // (the cache has room for it: icd_unet_kv_cache_bytes)
+            have = io->kv_cache_valid != 0;
+        } else {
+            k_all = alloc<half_t>(k_elems);
+            vt_all = alloc<half_t>(v_elems);
+            if (split(ICD_SPLIT_QK)) k_all_c = (unsigned char*)alloc_aux(k_elems);
+        }
+        const half_t* wk = Wh("attn2_k_cat.weight", (long long)N * X);      // (a walk over a valid cache still checks that the weights are bound)
+        const half_t* wv = Wh("attn2_v_cat.weight", (long long)N * X);
+        if (!have) {
+            icd_gemm_desc k = dense(io->context, X, Mc, X, wk, N, k_all, N);
+            set_aux(k, nullptr, k_all_c);
+            launch(k);
+            icd_gemm_desc v = dense(io->context, X, Mc, X, wv, N, vt_all, ldvc);
+            v.flags = ICD_GEMM_OUT_TRANS; v.rows_per_sample = nctx;
+            launch(v);
+        }
+        kv_off = 0;
+        return ICD_OK;
+    }
+
+    // conv_in on the matrix cores: pack the 4-channel NCHW latent to [B*HW, 8] and run the implicit GEMM (K = 72)
+    Act conv_in() {
+        const int ch0 = u->cfg.block_out_channels[0], HW0 = H0 * W0;
+        Act h{alloc<half_t>((long long)B * HW0 * ch0), ch0};
+        half_t* lat8 = alloc<half_t>((long long)B * HW0 * 8);
+        if (ok() && !dry) {
+            ProfScope ps(st, ICD_PROF_MISC, 0.0, (double)B * HW0 * 24.0);
+            run(icd_pack_latent(io->sample, io->sample_is_f32, B, HW0, lat8, st));
+        }
+        h.aux = alloc_aux((long long)B * HW0 * ch0);                          // residual of down_blocks.0.resnets.0
+        icd_gemm_desc d = conv(Act{lat8, 8}, nullptr, H0, W0, 3, 1, 0, Wh("conv_in.weight8", 72LL * ch0), ch0, h.p);
+        d.bias = Wf("conv_in.bias", ch0);
+        set_aux(d, nullptr, h.aux);
+        launch(d);
+        release(lat8);
+        return h;
+    }
+
+    // Downsample2D of level i: conv3x3 stride 2 on h [B, Hh, Ww, Cout]; h stays alive (it is on the skip stack)
+    Act downsample(int i, Act& h, int Hh, int Ww) {
+        const int Cout = h.C;
+        const std::string dp = "down_blocks." + std::to_string(i) + ".downsamplers.0.conv";
+        const long long out_elems = (long long)B * (Hh / 2) * (Ww / 2) * Cout;
+        Act dn{alloc<half_t>(out_elems), Cout};
+        // (it is a residual only where the next level keeps the channel count: SD1.5's last level)
+        if (split(ICD_SPLIT_SAMPLER_OUT) || u->cfg.block_out_channels[i + 1] == Cout) dn.aux = alloc_aux(out_elems);
+        const bool sd = split(ICD_SPLIT_DOWN);       // the stride-2 conv over [h | lo] against per-tap [W | W]
+        const Act la{sd ? expand(h.aux, (long long)B * Hh * Ww * Cout) : nullptr, Cout};
+        icd_gemm_desc d = conv(h, sd ? &la : nullptr, Hh, Ww, 3, 2, 0, Wh(dp + (sd ? ".weight2" : ".weight"), (sd ? 18LL : 9LL) * Cout * Cout), Cout, dn.p);
+        d.bias = Wf(dp + ".bias", Cout);
+        set_aux(d, nullptr, dn.aux);
+        launch(d, sd ? 9LL * Cout : 0);
+        release(la.p);
+        if (u->resid_mode != 3) free_aux(h);
+        return dn;
+    }
+
+    // Upsample2D of up block i: nearest 2x + conv3x3 on h [B, Hh, Ww, Cout], which it releases
+    Act upsample(int i, Act& h, int Hh, int Ww) {
+        const int L = u->cfg.num_levels, Cout = h.C;
+        const std::string upn = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
+        Act up{alloc<half_t>((long long)B * (Hh * 2) * (Ww * 2) * Cout), Cout};
+        if (split(ICD_SPLIT_SAMPLER_OUT)) up.aux = alloc_aux((long long)B * (Hh * 2) * (Ww * 2) * Cout);
+        // (the last upsampler - at the output resolution, damped by nothing downstream - or every one: ICD_SPLIT_UP_ALL)
+        const bool sup = split(ICD_SPLIT_UP) && (i == L - 2 || split(ICD_SPLIT_UP_ALL));
+        const long long hin = (long long)B * Hh * Ww;
+        // (the phase form maps output rows with a divide by the input width: icd_gemm needs out_remap_w >= 2.  A level one pixel wide -
+        //  latents of 2^(levels - 1) pixels, which icd_unet_forward accepts - takes the 3 x 3 form, as before round 5)
+        const bool phases = u->up_phases && Ww >= 2;
+        half_t* lo = nullptr;                // the upsampling conv over [h | lo]
+        if (sup && phases) {           // ... in the phase form over [h | lo | h] against [W_hi | W_hi | W_lo] (the tap sums are not fp16 numbers)
+            lo = alloc<half_t>(hin * 2 * Cout);
+            if (ok() && !dry) {
+                ProfScope ps(st, ICD_PROF_MISC, 0.0, 7.0 * (double)hin * Cout);
+                run(icd_carry_expand2(h.aux, h.p, hin, Cout, lo, st));
+            }
+        } else if (sup) lo = expand(h.aux, hin * Cout);
+        const Act la{lo, (sup && phases) ? 2 * Cout : Cout};
+        // algorithmic K 9 Cout - per phase: a quarter of the output pixels x all 9 taps of the reference's conv
+        auto finish = [&](icd_gemm_desc& d) { d.bias = Wf(upn + ".bias", Cout); set_aux(d, nullptr, up.aux); launch(d, 9LL * Cout); };
+        if (phases) {
+            // nearest 2x + conv3x3 as four 2 x 2 convs on the input grid, one per output pixel phase: 16 tap GEMMs instead of 36
+            for (int ph = 0; ph < 4 && ok(); ++ph) {
+                const std::string wn = upn + (sup ? ".phase3." : ".phase.") + std::to_string(ph);
+                icd_gemm_desc d = conv(h, sup ? &la : nullptr, Hh, Ww, 3, 1, 0, Wh(wn, (sup ? 12LL : 4LL) * Cout * Cout), Cout, up.p);
+                conv_phase(d, ph);
+                finish(d);
+            }
+        } else {
+            icd_gemm_desc d = conv(h, sup ? &la : nullptr, Hh, Ww, 3, 1, 1, Wh(upn + (sup ? ".weight2" : ".weight"), (sup ? 18LL : 9LL) * Cout * Cout), Cout, up.p);
+            finish(d);
+        }
+        release(lo);
+        free_act(h);
+        return up;
+    }
+
+    void conv_out(Act& h) {
+        const icd_unet_config& c = u->cfg;
+        const int ch0 = c.block_out_channels[0], HW0 = H0 * W0;
+        half_t* n = alloc<half_t>((long long)B * HW0 * ch0);
+        groupnorm(h, nullptr, HW0, Wf("conv_norm_out.weight", ch0), Wf("conv_norm_out.bias", ch0), 1e-5f, 1, n);
+        free_act(h);
+        const half_t* wo = Wh("conv_out.weight", 9LL * ch0 * c.out_channels);
+        const float* bo = Wf("conv_out.bias", c.out_channels);
+        if (ok() && !dry) {
+            ProfScope ps(st, ICD_PROF_MISC, 2.0 * B * (double)HW0 * 9 * ch0 * c.out_channels, 0.0);
+            run(icd_conv_out(n, B, H0, W0, ch0, wo, bo, io->eps, io->sample_is_f32, st));
+        }
+        release(n);
+    }
+
+    // ---------------------------------------------------------------------------------------------- the walk
     int forward() {
         const icd_unet_config& c = u->cfg;
-        const int L = c.num_levels, ch0 = c.block_out_channels[0], temb = ch0 * 4;
-        const int HW0 = H0 * W0;
-        gn_ws = alloc<float>(icd_groupnorm_ws_floats(B, HW0, c.norm_groups));
-        if (split(ICD_SPLIT_TEMB)) {
-            const int rc = time_embedding_precise();
-            if (rc != ICD_OK) return rc;
-        } else {
-        // ---------------- time embedding: Timesteps -> (+cond_proj) -> Linear -> SiLU -> Linear (+ SDXL add_embedding)
-        half_t* tsin = alloc<half_t>((long long)B * ch0);
-        if (ok() && !dry) run(icd_sinusoid(io->timesteps, B, ch0, 0, tsin, st));
-        half_t* tin = tsin;
-        if (c.time_cond_proj_dim > 0 && (dry ? true : io->timestep_cond != nullptr)) {
-            tin = alloc<half_t>((long long)B * ch0);
-            linear((const half_t*)io->timestep_cond, c.time_cond_proj_dim, B, c.time_cond_proj_dim,
-                   Wh("time_embedding.cond_proj.weight", (long long)ch0 * c.time_cond_proj_dim), ch0, nullptr, tsin, ch0, tin, ch0);
-        }
-        half_t* e1 = alloc<half_t>((long long)B * temb);
-        linear(tin, ch0, B, ch0, Wh("time_embedding.linear_1.weight", (long long)temb * ch0), temb, Wf("time_embedding.linear_1.bias", temb),
-               nullptr, 0, e1, temb);
-        if (ok() && !dry) run(icd_silu(e1, (long long)B * temb, e1, st));
-        half_t* emb = alloc<half_t>((long long)B * temb);
-        linear(e1, temb, B, temb, Wh("time_embedding.linear_2.weight", (long long)temb * temb), temb, Wf("time_embedding.linear_2.bias", temb),
-               nullptr, 0, emb, temb);
-        if (c.add_in_dim > 0) {
-            const int tdim = c.addition_time_embed_dim, pooled = c.add_in_dim - 6 * tdim;
-            half_t* tid = alloc<half_t>((long long)B * 6 * tdim);
-            if (ok() && !dry) {
-                if (!io->time_ids || !io->text_embeds) { icd_set_error("SDXL forward needs text_embeds and time_ids"); return ICD_ERR_INVALID_ARG; }
-                run(icd_sinusoid(io->time_ids, B * 6, tdim, 0, tid, st));
-            }
-            half_t* a1 = alloc<half_t>((long long)B * temb);
-            // Linear over cat([text_embeds, time_embeds]) without materialising the concat: 1x1 "conv" with two sources
-            Act s0{(half_t*)io->text_embeds, pooled}, s1{tid, 6 * tdim};
-            const int saveB = B;
-            {
-                icd_gemm_desc d; memset(&d, 0, sizeof(d));
-                d.a0 = s0.p; d.a1 = s1.p; d.w = Wh("add_embedding.linear_1.weight", (long long)temb * c.add_in_dim);
-                d.bias = Wf("add_embedding.linear_1.bias", temb); d.out = a1;
-                d.C0 = s0.C; d.C1 = s1.C; d.M = saveB; d.N = temb; d.K = c.add_in_dim; d.Nw = temb; d.ldw = d.K; d.ldo = temb;
-                d.rows_per_sample = 1; d.mode = 1; d.Hin = d.Win = d.Hout = d.Wout = 1; d.ksize = 1; d.stride = 1; d.batch = 1; d.zdiv = 1; d.alpha = 1.f;
-                gemm_desc(d);
-            }
-            if (ok() && !dry) run(icd_silu(a1, (long long)B * temb, a1, st));
-            linear(a1, temb, B, temb, Wh("add_embedding.linear_2.weight", (long long)temb * temb), temb, Wf("add_embedding.linear_2.bias", temb),
-                   emb, temb, emb, temb);
-            release(a1); release(tid);
-        }
-        if (ok() && !dry) run(icd_silu(emb, (long long)B * temb, e1, st));      // e1 := SiLU(emb), shared by every resnet
-        temb_all = alloc<half_t>((long long)B * u->temb_total);
-        linear(e1, temb, B, temb, Wh("time_emb_proj_cat.weight", (long long)u->temb_total * temb), u->temb_total,
-               Wf("time_emb_proj_cat.bias", u->temb_total), nullptr, 0, temb_all, u->temb_total);
-        release(e1); release(emb); if (tin != tsin) release(tin); release(tsin);
-        }
+        const int L = c.num_levels;
+        gn_ws = alloc<float>(icd_groupnorm_ws_floats(B, H0 * W0, c.norm_groups));
+        int rc = split(ICD_SPLIT_TEMB) ? time_embedding_precise() : time_embedding_fp16();
+        if (rc != ICD_OK) return rc;
         temb_off = 0;
-        // every cross-attention K / V projection depends on the context only: two GEMMs for the whole forward
-        {
-            const int X = c.cross_dim, Mc = B * nctx, ldvc = (nctx + 7) / 8 * 8;
-            const long long k_elems = (long long)Mc * u->kv_total, v_elems = (long long)B * u->kv_total * ldvc;
-            bool have = false;
-            if (!dry && io->kv_cache) {                  // caller-owned cache of the context projections (icd_unet_io.kv_cache)
-                if (io->kv_cache_bytes < (k_elems + v_elems) * 2 + k_elems) {
-                    icd_set_error("icd_unet_forward: kv_cache too small (%lld bytes given); query icd_unet_kv_cache_bytes", (long long)io->kv_cache_bytes);
-                    return ICD_ERR_WORKSPACE;
-                }
-                k_all = (half_t*)io->kv_cache; vt_all = k_all + k_elems; kv_external = true;
-                if (split(ICD_SPLIT_QK)) k_all_c = (unsigned char*)(vt_all + v_elems);       // (the cache has room for it: icd_unet_kv_cache_bytes)
-                have = io->kv_cache_valid != 0;
-            } else {
-                k_all = alloc<half_t>(k_elems);
-                vt_all = alloc<half_t>(v_elems);
-                if (split(ICD_SPLIT_QK)) k_all_c = (unsigned char*)alloc_aux(k_elems);
-            }
-            if (!have) {
-                linear((const half_t*)io->context, X, Mc, X, Wh("attn2_k_cat.weight", (long long)u->kv_total * X), u->kv_total, nullptr,
-                       nullptr, 0, k_all, u->kv_total, 0, 0, nullptr, nullptr, nullptr, k_all_c);
-                linear((const half_t*)io->context, X, Mc, X, Wh("attn2_v_cat.weight", (long long)u->kv_total * X), u->kv_total, nullptr,
-                       nullptr, 0, vt_all, ldvc, ICD_GEMM_OUT_TRANS, nctx);
-            } else {                                     // (a finalize-style walk still checks that the weights are bound)
-                (void)Wh("attn2_k_cat.weight", (long long)u->kv_total * X); (void)Wh("attn2_v_cat.weight", (long long)u->kv_total * X);
-            }
-            kv_off = 0;
-        }
-
-        // ---------------- conv_in
-        std::vector<Act> skips;
-        std::vector<int> skipH;
-        Act h{alloc<half_t>((long long)B * HW0 * ch0), ch0};
-        {
-            // conv_in on the matrix cores: pack the 4-channel NCHW latent to [B*HW, 8] and run the implicit GEMM (K = 72)
-            half_t* lat8 = alloc<half_t>((long long)B * HW0 * 8);
-            if (ok() && !dry) {
-                ProfScope ps(true, st, ICD_PROF_MISC, 0.0, (double)B * HW0 * 24.0);
-                run(icd_pack_latent(io->sample, io->sample_is_f32, B, HW0, lat8, st));
-            }
-            Act l8{lat8, 8};
-            h.aux = alloc_aux((long long)B * HW0 * ch0);                          // residual of down_blocks.0.resnets.0
-            conv(l8, nullptr, H0, W0, 3, 1, 0, Wh("conv_in.weight8", 72LL * ch0), ch0, Wf("conv_in.bias", ch0), nullptr, 0, nullptr, h.p,
-                 nullptr, h.aux);
-            release(lat8);
-        }
+        if ((rc = context_kv()) != ICD_OK) return rc;
+        Act h = conv_in();
         // the skip stack keeps the fp16 tensors (their consumers concatenate them as GEMM / GroupNorm operands); the fp32 twin / error
         // carry of a tensor lives only until the one operator that uses it as a residual has run
         const bool sp = u->resid_mode == 3;
+        std::vector<Act> skips;
         auto skip_of = [&](const Act& a) { Act s{a.p, a.C}; if (sp) s.aux = a.aux; return s; };   // split mode: skips keep their carry
         skips.push_back(skip_of(h));
         int Hh = H0, Ww = W0;
         // ---------------- down
         for (int i = 0; i < L && ok(); ++i) {
-            const int Cout = c.block_out_channels[i];
+            const std::string blk = "down_blocks." + std::to_string(i);
             for (int j = 0; j < c.layers_per_block && ok(); ++j) {
-                const std::string rp = "down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j);
-                Act r = resnet(rp, h, nullptr, Hh, Ww, Cout);
+                Act r = resnet(blk + ".resnets." + std::to_string(j), h, nullptr, Hh, Ww, c.block_out_channels[i]);
                 // h stays alive: it is on the skip stack (its twin / carry has served as this resnet's residual)
                 if (!sp) free_aux(h);
                 h = r;
                 if (c.down_has_attn[i]) {
-                    Act t = transformer("down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), h, Hh, Ww,
-                                        c.transformer_layers[i], c.num_heads[i], 0);
+                    Act t = transformer(blk + ".attentions." + std::to_string(j), h, Hh, Ww, c.transformer_layers[i], c.num_heads[i], 0);
                     free_act(h);
                     h = t;
                 }
                 skips.push_back(skip_of(h));
             }
             if (i < L - 1) {
-                const std::string dp = "down_blocks." + std::to_string(i) + ".downsamplers.0.conv";
-                Act dn{alloc<half_t>((long long)B * (Hh / 2) * (Ww / 2) * Cout), Cout};
-                // (it is a residual only where the next level keeps the channel count: SD1.5's last level)
-                if (split(ICD_SPLIT_SAMPLER_OUT) || c.block_out_channels[i + 1] == Cout) dn.aux = alloc_aux((long long)B * (Hh / 2) * (Ww / 2) * Cout);
-                if (split(ICD_SPLIT_DOWN)) {         // the stride-2 conv over [h | lo] against per-tap [W | W]
-                    half_t* lo = expand(h.aux, (long long)B * Hh * Ww * Cout);
-                    Act la{lo, Cout};
-                    alg_k = 9LL * Cout;
-                    conv(h, &la, Hh, Ww, 3, 2, 0, Wh(dp + ".weight2", 18LL * Cout * Cout), Cout, Wf(dp + ".bias", Cout), nullptr, 0, nullptr, dn.p,
-                         nullptr, dn.aux);
-                    release(lo);
-                } else {
-                    conv(h, nullptr, Hh, Ww, 3, 2, 0, Wh(dp + ".weight", 9LL * Cout * Cout), Cout, Wf(dp + ".bias", Cout), nullptr, 0, nullptr, dn.p,
-                         nullptr, dn.aux);
-                    if (!sp) free_aux(h);
-                }
+                h = downsample(i, h, Hh, Ww);
                 Hh /= 2; Ww /= 2;
-                h = dn;
                 skips.push_back(skip_of(h));
             }
         }
@@ -798,92 +816,51 @@ struct Exec {
             if (!sp) free_aux(h);
             Act t = transformer("mid_block.attentions.0", r0, Hh, Ww, c.transformer_layers[L - 1], c.num_heads[L - 1], 1);
             free_act(r0);
-            Act r1 = resnet("mid_block.resnets.1", t, nullptr, Hh, Ww, Cm);
+            h = resnet("mid_block.resnets.1", t, nullptr, Hh, Ww, Cm);
             free_act(t);
-            h = r1;
         }
         // ---------------- up
         for (int i = 0; i < L && ok(); ++i) {
             const int lvl = L - 1 - i;
-            const int Cout = c.block_out_channels[lvl];
+            const std::string blk = "up_blocks." + std::to_string(i);
             for (int j = 0; j < c.layers_per_block + 1 && ok(); ++j) {
                 Act sk = skips.back(); skips.pop_back();
-                const std::string rp = "up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j);
-                Act r = resnet(rp, h, &sk, Hh, Ww, Cout);
-                free_act(h); release(sk.p); release(sk.aux);
+                Act r = resnet(blk + ".resnets." + std::to_string(j), h, &sk, Hh, Ww, c.block_out_channels[lvl]);
+                free_act(h); free_act(sk);
                 h = r;
                 if (c.up_has_attn[i]) {
-                    Act t = transformer("up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), h, Hh, Ww,
-                                        c.transformer_layers[lvl], c.num_heads[lvl], 2);
+                    Act t = transformer(blk + ".attentions." + std::to_string(j), h, Hh, Ww, c.transformer_layers[lvl], c.num_heads[lvl], 2);
                     free_act(h);
                     h = t;
                 }
                 if (!sp) free_aux(h);                // the next resnet concatenates h with a skip: Cin != Cout, its residual is the shortcut
             }                                        // (split mode: its GroupNorm and its split shortcut read the carry)
             if (i < L - 1) {
-                const std::string upn = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
-                Act up{alloc<half_t>((long long)B * (Hh * 2) * (Ww * 2) * Cout), Cout};
-                if (split(ICD_SPLIT_SAMPLER_OUT)) up.aux = alloc_aux((long long)B * (Hh * 2) * (Ww * 2) * Cout);
-                // (the last upsampler - at the output resolution, damped by nothing downstream - or every one: ICD_SPLIT_UP_ALL)
-                const bool sup = split(ICD_SPLIT_UP) && (i == L - 2 || split(ICD_SPLIT_UP_ALL));
-                const long long hin = (long long)B * Hh * Ww;
-                // (the phase form maps output rows with a divide by the input width: icd_gemm needs out_remap_w >= 2.  A level one pixel wide -
-                //  latents of 2^(levels - 1) pixels, which icd_unet_forward accepts - takes the 3 x 3 form, as before round 5)
-                const bool phases = u->up_phases && Ww >= 2;
-                half_t* lo = nullptr;                // the upsampling conv over [h | lo]
-                if (sup && phases) {           // ... in the phase form over [h | lo | h] against [W_hi | W_hi | W_lo] (the tap sums are not fp16 numbers)
-                    lo = alloc<half_t>(hin * 2 * Cout);
-                    if (ok() && !dry) {
-                        ProfScope ps(true, st, ICD_PROF_MISC, 0.0, 7.0 * (double)hin * Cout);
-                        run(icd_carry_expand2(h.aux, h.p, hin, Cout, lo, st));
-                    }
-                } else if (sup) lo = expand(h.aux, hin * Cout);
-                Act la{lo, (sup && phases) ? 2 * Cout : Cout};
-                if (phases) {
-                    // nearest 2x + conv3x3 as four 2 x 2 convs on the input grid, one per output pixel phase: 16 tap GEMMs instead of 36
-                    for (int ph = 0; ph < 4 && ok(); ++ph) {
-                        const std::string wn = upn + (sup ? ".phase3." : ".phase.") + std::to_string(ph);
-                        alg_k = 9LL * Cout;          // per phase: a quarter of the output pixels x all 9 taps of the reference's conv
-                        conv(h, sup ? &la : nullptr, Hh, Ww, 3, 1, 0, Wh(wn, (sup ? 12LL : 4LL) * Cout * Cout), Cout, Wf(upn + ".bias", Cout),
-                             nullptr, 0, nullptr, up.p, nullptr, up.aux, false, ph);
-                    }
-                } else {
-                    alg_k = 9LL * Cout;
-                    conv(h, sup ? &la : nullptr, Hh, Ww, 3, 1, 1, Wh(upn + (sup ? ".weight2" : ".weight"), (sup ? 18LL : 9LL) * Cout * Cout), Cout,
-                         Wf(upn + ".bias", Cout), nullptr, 0, nullptr, up.p, nullptr, up.aux);
-                }
-                release(lo);
-                free_act(h);
+                h = upsample(i, h, Hh, Ww);
                 Hh *= 2; Ww *= 2;
-                h = up;
             }
         }
-        // ---------------- out
-        half_t* n = alloc<half_t>((long long)B * HW0 * ch0);
-        groupnorm(h, nullptr, HW0, Wf("conv_norm_out.weight", ch0), Wf("conv_norm_out.bias", ch0), 1e-5f, 1, n);
-        free_act(h);
-        const half_t* wo = Wh("conv_out.weight", 9LL * ch0 * c.out_channels);
-        const float* bo = Wf("conv_out.bias", c.out_channels);
-        if (ok() && !dry) {
-            ProfScope ps(true, st, ICD_PROF_MISC, 2.0 * B * (double)HW0 * 9 * ch0 * c.out_channels, 0.0);
-            run(icd_conv_out(n, B, H0, W0, ch0, wo, bo, io->eps, io->sample_is_f32, st));
-        }
-        release(n);
+        conv_out(h);
         release(temb_all);
         if (!kv_external) { release(k_all); release(vt_all); release(k_all_c); }
         return status;
     }
 };
 
-int count_attn(const icd_unet_config& c) {
-    int n = 0;
+// sum of f(level) over every Transformer2DModel of the topology: down blocks, mid block, up blocks
+template <typename F> int sum_transformers(const icd_unet_config& c, F f) {
     const int L = c.num_levels;
-    for (int i = 0; i < L; ++i) if (c.down_has_attn[i]) n += c.layers_per_block * c.transformer_layers[i] * 2;
-    n += c.transformer_layers[L - 1] * 2;
-    for (int i = 0; i < L; ++i) if (c.up_has_attn[i]) n += (c.layers_per_block + 1) * c.transformer_layers[L - 1 - i] * 2;
+    int n = f(L - 1);
+    for (int i = 0; i < L; ++i) {
+        if (c.down_has_attn[i]) n += c.layers_per_block * f(i);
+        if (c.up_has_attn[i]) n += (c.layers_per_block + 1) * f(L - 1 - i);
+    }
     return n;
 }
-
+int count_attn(const icd_unet_config& c) { return sum_transformers(c, [&](int l) { return c.transformer_layers[l] * 2; }); }
+// sum of C over every transformer block (cross-attention K / V columns)
+int kv_total(const icd_unet_config& c) { return sum_transformers(c, [&](int l) { return c.transformer_layers[l] * c.block_out_channels[l]; }); }
+// sum of Cout over every resnet in execution order (the columns of time_emb_proj_cat)
 int temb_total(const icd_unet_config& c) {
     int t = 0;
     const int L = c.num_levels;
@@ -932,38 +909,6 @@ extern "C" int icd_unet_set_option(icd_unet* u, int32_t option, int32_t value) {
     return ICD_ERR_INVALID_ARG;
 }
 
-extern "C" int icd_profile_enable(int32_t enable) {
-    for (auto& r : g_prof) { g_ev_pool.push_back(r.a); g_ev_pool.push_back(r.b); }
-    g_prof.clear();
-    g_prof_on = enable != 0;
-    g_prof_mask = enable > 0 ? 0xffffffffu : (unsigned)(-enable);     // enable < 0: bit mask of the families to record
-    return ICD_OK;
-}
-
-extern "C" int icd_profile_read(icd_profile_row* rows, int32_t max_rows) {
-    ICD_CHECK_ARG(rows && max_rows >= ICD_PROF_KINDS, "icd_profile_read: need room for %d rows", ICD_PROF_KINDS);
-    for (int k = 0; k < ICD_PROF_KINDS; ++k) { rows[k].kind = k; rows[k].launches = 0; rows[k].ms = rows[k].flops = rows[k].bytes = rows[k].flops_executed = 0.0; }
-    for (auto& r : g_prof) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) { icd_set_error("icd_profile_read: events not complete (synchronise the stream first)"); return ICD_ERR_HIP; }
-        rows[r.kind].launches += 1; rows[r.kind].ms += ms; rows[r.kind].flops += r.flops; rows[r.kind].bytes += r.bytes;
-        rows[r.kind].flops_executed += r.xflops;
-    }
-    return ICD_PROF_KINDS;
-}
-
-extern "C" int icd_profile_dump(icd_profile_record* recs, int32_t max_recs) {
-    const int n = (int)std::min<size_t>(g_prof.size(), (size_t)std::max(0, max_recs));
-    for (int i = 0; i < n && recs; ++i) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, g_prof[i].a, g_prof[i].b) != hipSuccess) { icd_set_error("icd_profile_dump: events not complete"); return ICD_ERR_HIP; }
-        recs[i].kind = g_prof[i].kind; recs[i].M = g_prof[i].M; recs[i].N = g_prof[i].N; recs[i].K = g_prof[i].K; recs[i].aux = g_prof[i].aux;
-        recs[i].ms = ms; recs[i].flops = g_prof[i].flops;
-        recs[i].tile_m = g_prof[i].tile_m; recs[i].tile_n = g_prof[i].tile_n; recs[i].plan_flags = g_prof[i].plan_flags; recs[i].ksplit = g_prof[i].ksplit;
-    }
-    return recs ? n : (int)g_prof.size();
-}
-
 extern "C" int icd_unet_create(const icd_unet_config* cfg, icd_unet** out) {
     ICD_CHECK_ARG(cfg && out, "icd_unet_create: null argument");
     ICD_CHECK_ARG(cfg->num_levels >= 2 && cfg->num_levels <= 4, "icd_unet_create: num_levels must be 2..4");
@@ -981,14 +926,7 @@ extern "C" int icd_unet_create(const icd_unet_config* cfg, icd_unet** out) {
     u->cfg = *cfg;
     u->n_attn = count_attn(*cfg);
     u->temb_total = temb_total(*cfg);
-    {
-        const int L = cfg->num_levels;
-        int t = 0;
-        for (int i = 0; i < L; ++i) if (cfg->down_has_attn[i]) t += cfg->layers_per_block * cfg->transformer_layers[i] * cfg->block_out_channels[i];
-        t += cfg->transformer_layers[L - 1] * cfg->block_out_channels[L - 1];
-        for (int i = 0; i < L; ++i) if (cfg->up_has_attn[i]) t += (cfg->layers_per_block + 1) * cfg->transformer_layers[L - 1 - i] * cfg->block_out_channels[L - 1 - i];
-        u->kv_total = t;
-    }
+    u->kv_total = kv_total(*cfg);
     *out = u;
     return ICD_OK;
 }
