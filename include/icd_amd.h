@@ -329,6 +329,32 @@ int icd_attention_probs_ex(const void* q, const void* q_carry, const void* k, co
                            int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale,
                            const icd_probs_epilogue* epilogue, void* stream);
 
+/* What an attention entry would run for a shape (pure host function: nothing is enqueued, no HIP call, works without a GPU).  The
+ * query holds the arguments the dispatch reads: entry 0 = icd_attention_fused_ex (flags: ICD_ATTN_*), 1 = icd_attention_probs* (ldp;
+ * split: carries present; epi: 0 no epilogue, 1 acc / self_from_base, 2 the cross edit), 2 = icd_attention_masked.  It is the entry's
+ * own validation with every argument the query does not hold at a value that passes, then the entry's own planner: it refuses, with
+ * the entry's status and message, exactly what the entry refuses on these arguments alone.
+ * The answer: family 0 = attn_fused_kernel (tiled), 1 = attn_cross_kernel (K / V^T in registers), 2 = attn_probs_kernel,
+ * 3 = attn_masked_kernel; variant = the row of that family's instantiation table, variants = rows in it; the row's template parameters
+ * (KS, DT, QT, OCC, NST, MODE, DR, causal: tiled; KS, DT, STL and the run-time tiles_per_wave: cross; KS, SPLIT, EPI, FEW: probs;
+ * NT, DT: masked; a field the family does not have is 0); the grid and the dynamic LDS bytes of the launch. */
+typedef struct {
+    int32_t entry;
+    int32_t B, H, Nq, Nk, d;
+    int32_t ldp;
+    int32_t flags;
+    int32_t split, epi;
+} icd_attention_query;
+typedef struct {
+    int32_t family, variant, variants;
+    int32_t KS, DT, QT, OCC, NST, MODE, DR, causal;
+    int32_t STL, tiles_per_wave;
+    int32_t SPLIT, EPI, FEW;
+    int32_t NT;
+    int32_t grid_x, grid_y, grid_z, lds_bytes;
+} icd_attention_info;
+int icd_attention_plan(const icd_attention_query* q, icd_attention_info* out);
+
 /* Sinusoidal embeddings.  kind 0: diffusers Timesteps(dim, flip_sin_to_cos=True, shift=0) -> [cos || sin];
  * kind 1: guidance_scale_embedding (utils/generation.py:96-122) -> [sin || cos] of 1000*w, denominator half-1.
  * vals: fp32 [n] on device; out fp16 [n, dim]. */

@@ -76,6 +76,17 @@ class ProbsEpilogue(C.Structure):
                 ("self_from_base", C.c_int32), ("first_cond_row", C.c_int64), ("edit_count", C.c_int32), ("group_count", C.c_int32)]
 
 
+class AttentionQuery(C.Structure):
+    """icd_attention_query: entry 0 fused (flags), 1 probs (ldp, split, epi 0 / 1 / 2), 2 masked."""
+    _fields_ = [(n, C.c_int32) for n in ("entry", "B", "H", "Nq", "Nk", "d", "ldp", "flags", "split", "epi")]
+
+
+class AttentionInfo(C.Structure):
+    """icd_attention_info: family 0 tiled, 1 cross, 2 probs, 3 masked; variant = the row of that family's instantiation table."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "variant", "variants", "KS", "DT", "QT", "OCC", "NST", "MODE", "DR", "causal", "STL",
+                                         "tiles_per_wave", "SPLIT", "EPI", "FEW", "NT", "grid_x", "grid_y", "grid_z", "lds_bytes")]
+
+
 class GemmPlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32), ("ksplit", C.c_int32),
                 ("ln_inline", C.c_int32), ("xattn", C.c_int32), ("cfg", C.c_int32), ("group_m", C.c_int32)]
@@ -195,6 +206,7 @@ SIGNATURES = {
     "icd_conv_out_n": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_int32, C.c_void_p]),
     "icd_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo)]),
+    "icd_attention_plan": (C.c_int, [C.POINTER(AttentionQuery), C.POINTER(AttentionInfo)]),
     "icd_unet_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "icd_clip_preprocess": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
                             + [C.POINTER(C.c_float)] * 2 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -243,6 +255,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
+        if os.environ.get("ICD_AMD_LIB") and not hasattr(lib, name):
+            continue                               # another build, for A/B, may predate an entry: calling that entry then raises
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

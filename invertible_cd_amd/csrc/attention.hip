@@ -19,6 +19,7 @@
 //   * XCD-aware block order: the q-tiles of one (b, h) run on one XCD so its K/V stay in that XCD's L2.
 #include <type_traits>
 #include "attn_frag.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -1032,112 +1033,218 @@ __global__ __launch_bounds__(256, (KS <= 5 && !FEW && EPI == 0) ? 3 : 2) void at
     }
 }
 
-template <int KS, int DT>
-int launch_attn_cross(AttnK k, hipStream_t st) {
-    // tiles per wave: amortise the K / V^T fragment loads (24 x 1 KiB per wave from L2) but keep >= ~4 blocks per CU
-    // (round-3 sweep of 4 - 32 tiles per wave and 512 - 1024 blocks: within the noise of each other)
-    int tpw = 8;
-    while (tpw > 1 && (long long)((k.Nq + 128 * tpw - 1) / (128 * tpw)) * k.B * k.H < 1024) tpw >>= 1;
-    const int nchunk = (k.Nq + 128 * tpw - 1) / (128 * tpw);
-    if (k.Nk <= 80) hipLaunchKernelGGL((attn_cross_kernel<KS, DT, 5>), dim3(nchunk * k.B * k.H), dim3(256), 0, st, k, tpw);
-    else hipLaunchKernelGGL((attn_cross_kernel<KS, DT, 6>), dim3(nchunk * k.B * k.H), dim3(256), 0, st, k, tpw);
+// ---------------------------------------------------------------------------------------------------------------
+// Host: every entry is validate -> plan -> launch (attn_host.h), over one table of instantiations per kernel family.
+// ---------------------------------------------------------------------------------------------------------------
+struct TiledRow { int KS, DT, QT, OCC, NST, MODE, DR; bool CAUSAL; };
+// A causal twin follows its row (fused_plan adds `causal` to the row's name): every one-query-tile-per-wave kernel of MODE 0, and the
+// head-dim-64 MODE 2 kernel (the CLIP text encoders).
+// (round 3, same-box round-robin A/B at 4096 x 4096: one query tile per wave, three blocks per CU and a 3-stage ring are all
+//  1 - 12 % slower than the configurations below with MODE 1 / 2; profiles/r03_attn_variants.txt)
+enum { T16, T16C, T32, T32C, T40FW, T40F, T64F, T64FC, T80F, T48W, T48, T48C, T64, T64C, T80, T80C, T96, T96C, T128, T128C, T160, T160C, TILED_ROWS };
+constexpr TiledRow TILED[TILED_ROWS] = {
+    // KS DT QT OCC NST MODE DR CAUSAL
+    {1, 1, 1, 2, 2, 0, 0, false}, {1, 1, 1, 2, 2, 0, 0, true},       // T16
+    {2, 1, 1, 2, 2, 0, 0, false}, {2, 1, 1, 2, 2, 0, 0, true},       // T32
+    {3, 2, 2, 2, 2, 1, 3, false},                                    // T40FW: P.V on 16-row tiles (48 rows, not 64)
+    {3, 2, 1, 2, 2, 1, 0, false},                                    // T40F
+    {4, 2, 1, 2, 2, 2, 0, false}, {4, 2, 1, 2, 2, 2, 0, true},       // T64F
+    {5, 3, 1, 2, 2, 2, 0, false},                                    // T80F
+    {3, 2, 2, 2, 2, 0, 0, false},                                    // T48W
+    {3, 2, 1, 2, 2, 0, 0, false}, {3, 2, 1, 2, 2, 0, 0, true},       // T48
+    {4, 2, 1, 2, 2, 0, 0, false}, {4, 2, 1, 2, 2, 0, 0, true},       // T64: QT = 2 spills at d = 64 (measured slower)
+    {5, 3, 1, 2, 2, 0, 0, false}, {5, 3, 1, 2, 2, 0, 0, true},       // T80
+    {6, 3, 1, 2, 2, 0, 0, false}, {6, 3, 1, 2, 2, 0, 0, true},       // T96
+    {8, 4, 1, 2, 2, 0, 0, false}, {8, 4, 1, 2, 2, 0, 0, true},       // T128
+    // head dim 160 (SD1.5's 16 x 16 / 8 x 8 levels): its accumulators and fragments do not fit the 256 registers of two waves per SIMD
+    // (187 spilt); one wave per SIMD with the whole register file is 10 - 35 % faster (profiles/r03_attn_small_kernels.txt)
+    {10, 5, 1, 1, 2, 0, 0, false}, {10, 5, 1, 1, 2, 0, 0, true},     // T160
+};
+constexpr int tiled_lds(const TiledRow& r) { return r.NST * (64 * 2 * r.KS * 16 + (r.DR ? r.DR * 16 : r.DT * 32) * 128); }
+constexpr bool tiled_twins_follow() {
+    for (int i = 0; i < TILED_ROWS; ++i) {
+        const TiledRow &r = TILED[i], &b = TILED[i ? i - 1 : 0];
+        if (r.CAUSAL && !(i && !b.CAUSAL && r.KS == b.KS && r.DT == b.DT && r.QT == b.QT && r.OCC == b.OCC && r.NST == b.NST && r.MODE == b.MODE && r.DR == b.DR))
+            return false;
+    }
+    return true;
+}
+static_assert(tiled_twins_follow(), "a CAUSAL row of TILED must follow its non-causal twin");
+
+struct CrossRow { int KS, DT, STL; };
+constexpr CrossRow CROSS[6] = {{2, 1, 5}, {2, 1, 6}, {3, 2, 5}, {3, 2, 6}, {4, 2, 5}, {4, 2, 6}};      // row = 2 (d <= 32, <= 48, <= 64) + (Nk > 80)
+
+int fused_validate(const AttnArgs& a, int32_t flags) {
+    ICD_CHECK_ARG((flags & ~(ICD_ATTN_CAUSAL | ICD_ATTN_Q_PRESCALED | ICD_ATTN_TUNE_MODE0)) == 0, "icd_attention_fused: unknown flags 0x%x", flags);
+    ICD_CHECK_ARG(!(flags & ICD_ATTN_CAUSAL) || a.Nq == a.Nk, "icd_attention_fused: the causal mask needs Nq == Nk");
+    ICD_CHECK_ARG(a.d > 0 && a.d % 8 == 0 && a.d <= 160, "icd_attention_fused: head dim must be a multiple of 8, <= 160 (got %d)", a.d);
+    return attn_check_common("icd_attention_fused", a);
+}
+
+void fused_plan(int B, int H, int Nq, int Nk, int d, int flags, AttnPlan* p) {
+    *p = AttnPlan{};
+    p->grid_y = p->grid_z = 1;
+    const int causal = (flags & ICD_ATTN_CAUSAL) ? 1 : 0;
+    const long long bh = (long long)B * H;
+    // cross-attention with enough query tiles to give every wave >= 2 of them (so the 24 KiB of K / V^T fragments per
+    // wave amortise and the next Q tile prefetches): K / V^T fragments live in registers.  Shorter problems (SDXL's
+    // 1024-query layers at batch 8) are launch + latency bound either way (~20 us for 42 MB) and stay on the tiled kernel.
+    if (Nk > 64 && Nk <= 96 && d <= 64 && !causal && (Nq + 127) / 128 * bh >= 2048) {
+        // tiles per wave: amortise the K / V^T fragment loads (24 x 1 KiB per wave from L2) but keep >= ~4 blocks per CU
+        // (round-3 sweep of 4 - 32 tiles per wave and 512 - 1024 blocks: within the noise of each other)
+        int tpw = 8;
+        while (tpw > 1 && (Nq + 128 * tpw - 1) / (128 * tpw) * bh < 1024) tpw >>= 1;
+        p->family = ATTN_CROSS; p->variants = 6;
+        p->variant = 2 * (d <= 32 ? 0 : d <= 48 ? 1 : 2) + (Nk <= 80 ? 0 : 1);
+        const CrossRow& r = CROSS[p->variant];
+        p->KS = r.KS; p->DT = r.DT; p->STL = r.STL; p->tiles_per_wave = tpw;
+        p->grid_x = (Nq + 128 * tpw - 1) / (128 * tpw) * B * H;
+        return;
+    }
+    // MODE 1 / 2 kernels (exponent offset subtracted by the MFMA); a causal mask has the fast form at head dim 64 only
+    const bool fast = (flags & ICD_ATTN_Q_PRESCALED) && !(flags & ICD_ATTN_TUNE_MODE0) && (!causal || d == 64);
+    // two query tiles per wave when the sequence is long enough to still fill the chip with 256-row workgroups
+    const bool wide = (Nq + 255) / 256 * bh >= 512 && Nk >= 256 && !causal;
+    p->family = ATTN_TILED; p->variants = TILED_ROWS;
+    if (d <= 16) p->variant = T16 + causal;
+    else if (d <= 32) p->variant = T32 + causal;
+    else if (fast && d == 40) p->variant = wide ? T40FW : T40F;          // (fast at 40 / 80 and wide: never causal)
+    else if (fast && d == 64) p->variant = T64F + causal;
+    else if (fast && d == 80) p->variant = T80F;
+    else if (d <= 48) p->variant = wide ? T48W : T48 + causal;
+    else if (d <= 64) p->variant = T64 + causal;
+    else if (d <= 80) p->variant = T80 + causal;
+    else if (d <= 96) p->variant = T96 + causal;
+    else if (d <= 128) p->variant = T128 + causal;
+    else p->variant = T160 + causal;
+    const TiledRow& r = TILED[p->variant];
+    p->KS = r.KS; p->DT = r.DT; p->QT = r.QT; p->OCC = r.OCC; p->NST = r.NST; p->MODE = r.MODE; p->DR = r.DR; p->causal = r.CAUSAL;
+    p->grid_x = (Nq + 128 * r.QT - 1) / (128 * r.QT) * B * H;
+    p->lds_bytes = tiled_lds(r);
+}
+
+template <int ROW>
+int tiled_launch_row(const AttnPlan& p, const AttnK& k, hipStream_t st) {
+    constexpr TiledRow R = TILED[ROW];
+    static_assert(tiled_lds(R) * R.OCC <= 160 * 1024, "LDS ring x occupancy exceeds the CU's 160 KiB");
+    static std::atomic<unsigned long long> armed{0};
+    return icd_launch_lds(armed, "icd_attention_fused", &attn_fused_kernel<R.KS, R.DT, R.QT, R.OCC, R.NST, R.MODE, R.CAUSAL, R.DR>, dim3(p.grid_x),
+                          dim3(256), tiled_lds(R), st, k);
+}
+template <int ROW>
+int cross_launch_row(const AttnPlan& p, const AttnK& k, hipStream_t st) {
+    constexpr CrossRow R = CROSS[ROW];
+    hipLaunchKernelGGL((attn_cross_kernel<R.KS, R.DT, R.STL>), dim3(p.grid_x), dim3(256), 0, st, k, p.tiles_per_wave);
     ICD_CHECK_LAUNCH("icd_attention_fused(cross)");
     return ICD_OK;
 }
-
-template <int KS, int DT, int QT, int OCC, int NST, int MODE, bool CAUSAL, int DR = 0>
-int launch_attn_c(AttnK k, hipStream_t st) {
-    constexpr int smem = NST * (64 * 2 * KS * 16 + (DR ? DR * 16 : DT * 32) * 128);
-    static_assert(smem * OCC <= 160 * 1024, "LDS ring x occupancy exceeds the CU's 160 KiB");
-    static std::atomic<unsigned long long> armed{0};
-    k.nqt = (k.Nq + 128 * QT - 1) / (128 * QT);
-    return icd_launch_lds(armed, "icd_attention_fused", &attn_fused_kernel<KS, DT, QT, OCC, NST, MODE, CAUSAL, DR>, dim3(k.nqt * k.B * k.H), dim3(256),
-                          smem, st, k);
-}
-template <int KS, int DT, int QT, int OCC = 2, int NST = 2, int MODE = 0, int DR = 0>
-int launch_attn(AttnK k, hipStream_t st) {
-    // causal instantiations: every one-query-tile-per-wave kernel of MODE 0, and the head-dim-64 MODE 2 kernel (the CLIP text
-    // encoders); icd_attention_fused_ex routes causal calls to those
-    if constexpr (QT == 1 && (MODE == 0 || (MODE == 2 && KS == 4))) { if (k.causal) return launch_attn_c<KS, DT, QT, OCC, NST, MODE, true>(k, st); }
-    if (k.causal) { icd_set_error("icd_attention_fused: internal: no causal instantiation for this tile"); return ICD_ERR_UNSUPPORTED; }
-    return launch_attn_c<KS, DT, QT, OCC, NST, MODE, false, DR>(k, st);
+int fused_launch(const AttnPlan& p, const AttnK& k, hipStream_t st) {
+    if (p.family == ATTN_CROSS)
+        return attn_launch_row(p.variant, [&](auto row) { return cross_launch_row<decltype(row)::value>(p, k, st); }, std::make_index_sequence<6>{});
+    return attn_launch_row(p.variant, [&](auto row) { return tiled_launch_row<decltype(row)::value>(p, k, st); }, std::make_index_sequence<TILED_ROWS>{});
 }
 
-}  // namespace
+struct ProbsRow { int KS; bool SPLIT; int EPI; bool FEW; };      // EPI 2 (the cross edit: <= 80 keys) exists as FEW only
+constexpr ProbsRow PROBS[40] = {                                 // row = 10 (d <= 48, <= 80, <= 128, <= 160) + 5 SPLIT + (EPI == 2 ? 4 : 2 EPI + FEW)
+    {3, false, 0, false}, {3, false, 0, true}, {3, false, 1, false}, {3, false, 1, true}, {3, false, 2, true},
+    {3, true, 0, false}, {3, true, 0, true}, {3, true, 1, false}, {3, true, 1, true}, {3, true, 2, true},
+    {5, false, 0, false}, {5, false, 0, true}, {5, false, 1, false}, {5, false, 1, true}, {5, false, 2, true},
+    {5, true, 0, false}, {5, true, 0, true}, {5, true, 1, false}, {5, true, 1, true}, {5, true, 2, true},
+    {8, false, 0, false}, {8, false, 0, true}, {8, false, 1, false}, {8, false, 1, true}, {8, false, 2, true},
+    {8, true, 0, false}, {8, true, 0, true}, {8, true, 1, false}, {8, true, 1, true}, {8, true, 2, true},
+    {10, false, 0, false}, {10, false, 0, true}, {10, false, 1, false}, {10, false, 1, true}, {10, false, 2, true},
+    {10, true, 0, false}, {10, true, 0, true}, {10, true, 1, false}, {10, true, 1, true}, {10, true, 2, true},
+};
 
-extern "C" int icd_attention_fused_ex(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H,
-                                      int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
-                                      int64_t vt_batch_stride, float scale, int32_t flags, void* stream);
+struct ProbsArgs {
+    const void *q, *qc, *k, *kc;
+    void* probs;
+    int32_t B, H, Nq, Nk, d, ldq, ldk, ldp;
+    float scale;
+    const icd_probs_epilogue* epi;
+};
+// first conditional sample, and samples per prompt group, of an epilogue
+int probs_b0(const ProbsArgs& a) { return a.epi->first_cond_row > 0 ? (int)(a.epi->first_cond_row / a.H) : a.epi->first_cond_sample; }
+int probs_groups(const ProbsArgs& a) { return a.epi->group_count > 1 ? a.epi->group_count : 1; }
 
-static int attention_probs_run(const void* q, const void* qc, const void* k, const void* kc, void* probs, int32_t B, int32_t H, int32_t Nq,
-                               int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale, void* stream,
-                               const icd_probs_epilogue* epi = nullptr) {
-    ICD_CHECK_ARG(q && k && probs, "icd_attention_probs: null pointer");
-    ICD_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "icd_attention_probs: empty shape");
+int probs_validate(const ProbsArgs& a) {
+    const int32_t B = a.B, H = a.H, Nk = a.Nk, d = a.d;
+    ICD_CHECK_ARG(a.q && a.k && a.probs, "icd_attention_probs: null pointer");
+    ICD_CHECK_ARG(B > 0 && H > 0 && a.Nq > 0 && Nk > 0, "icd_attention_probs: empty shape");
     ICD_CHECK_ARG(d > 0 && d % 8 == 0 && d <= 160, "icd_attention_probs: head dim must be a multiple of 8, <= 160 (got %d)", d);
-    ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldp % 8 == 0 && ldp >= Nk, "icd_attention_probs: leading dims must be 16-byte aligned, ldp >= Nk");
-    ICD_CHECK_ARG(scale > 0.f, "icd_attention_probs: scale must be positive");
+    ICD_CHECK_ARG(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldp % 8 == 0 && a.ldp >= Nk, "icd_attention_probs: leading dims must be 16-byte aligned, ldp >= Nk");
+    ICD_CHECK_ARG(a.scale > 0.f, "icd_attention_probs: scale must be positive");
     ICD_CHECK_ARG((long long)B * H <= 65535, "icd_attention_probs: B * H exceeds the grid limit");
-    ICD_CHECK_ARG(ldq >= (long long)H * d && ldk >= (long long)H * d, "icd_attention_probs: ldq and ldk must be >= H * d");
-    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)probs) % 16 == 0 && ((uintptr_t)qc | (uintptr_t)kc) % 8 == 0,
+    ICD_CHECK_ARG(a.ldq >= (long long)H * d && a.ldk >= (long long)H * d, "icd_attention_probs: ldq and ldk must be >= H * d");
+    ICD_CHECK_ARG(((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.probs) % 16 == 0 && ((uintptr_t)a.qc | (uintptr_t)a.kc) % 8 == 0,
                   "icd_attention_probs: q, k and probs must be 16-byte aligned, the carries 8-byte");
-    ICD_CHECK_ARG(!epi || (uintptr_t)epi->acc % 16 == 0, "icd_attention_probs_ex: acc must be 16-byte aligned");
-    ProbsK a;
-    a.q = (const half_t*)q; a.k = (const half_t*)k; a.p = (half_t*)probs;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldp = ldp;
-    a.scale_log2 = scale * ATTN_LOG2E;
-    a.qc = (const unsigned char*)qc; a.kc = (const unsigned char*)kc;
-    ProbsEpi ep{nullptr, nullptr, nullptr, 0, 0, 1};
-    if (epi) {
-        ICD_CHECK_ARG(epi->first_cond_sample >= 0 && epi->first_cond_sample < B, "icd_attention_probs_ex: first_cond_sample out of range");
-        ICD_CHECK_ARG(!epi->edit_At || (epi->edit_D && Nk <= 80 && ldp <= 96),
-                      "icd_attention_probs_ex: the cross-attention edit needs edit_D, <= 80 keys and a base + >= 1 edited prompt");
-        ep.acc = (half_t*)epi->acc; ep.At = (const half_t*)epi->edit_At; ep.D = epi->edit_D;
-        ep.b0 = epi->first_cond_row > 0 ? (int)(epi->first_cond_row / H) : epi->first_cond_sample; ep.self_base = epi->self_from_base != 0;
-        ICD_CHECK_ARG(epi->first_cond_row % H == 0 && ep.b0 < B, "icd_attention_probs_ex: first_cond_row must be a multiple of H inside the batch");
-        ICD_CHECK_ARG(!(ep.At || ep.self_base) || B - ep.b0 >= 2, "icd_attention_probs_ex: an edit needs a base prompt and at least one edited prompt");
-        const int groups = epi->group_count > 1 ? epi->group_count : 1;
-        ICD_CHECK_ARG(groups == 1 || epi->edit_count > 0, "icd_attention_probs_ex: group_count %d needs edit_count > 0", epi->group_count);
-        ICD_CHECK_ARG(groups > 1 || epi->edit_count <= 0 || epi->edit_count == B - ep.b0 - 1,
-                      "icd_attention_probs_ex: edit_count %d does not match the %d edited samples of the launch", epi->edit_count, B - ep.b0 - 1);
-        ICD_CHECK_ARG(groups == 1 || (long long)(B - ep.b0) == (long long)groups * (epi->edit_count + 1),
-                      "icd_attention_probs_ex: %d conditional samples are not %d groups of %d prompts", B - ep.b0, groups, epi->edit_count + 1);
-        ep.P = groups > 1 ? epi->edit_count + 1 : B - ep.b0;
-    }
-    const bool use_epi = ep.acc || ep.At || ep.self_base;
-    const dim3 grid((unsigned)((Nq + 127) / 128), (unsigned)(B * H));
-    hipStream_t st = (hipStream_t)stream;
-#define ICD_PROBS(SP, EP, FW)                                                                                  \
-    do {                                                                                                      \
-        if (d <= 48) hipLaunchKernelGGL((attn_probs_kernel<3, SP, EP, FW>), grid, dim3(256), 0, st, a, ep);       \
-        else if (d <= 80) hipLaunchKernelGGL((attn_probs_kernel<5, SP, EP, FW>), grid, dim3(256), 0, st, a, ep);  \
-        else if (d <= 128) hipLaunchKernelGGL((attn_probs_kernel<8, SP, EP, FW>), grid, dim3(256), 0, st, a, ep); \
-        else hipLaunchKernelGGL((attn_probs_kernel<10, SP, EP, FW>), grid, dim3(256), 0, st, a, ep);              \
-    } while (0)
-#define ICD_PROBS2(SP, EP) do { if (ldp <= 96) ICD_PROBS(SP, EP, true); else ICD_PROBS(SP, EP, false); } while (0)
-    if (qc || kc) { if (ep.At) ICD_PROBS(true, 2, true); else if (use_epi) ICD_PROBS2(true, 1); else ICD_PROBS2(true, 0); }
-    else { if (ep.At) ICD_PROBS(false, 2, true); else if (use_epi) ICD_PROBS2(false, 1); else ICD_PROBS2(false, 0); }
-#undef ICD_PROBS2
-#undef ICD_PROBS
+    const icd_probs_epilogue* epi = a.epi;
+    if (!epi) return ICD_OK;
+    ICD_CHECK_ARG((uintptr_t)epi->acc % 16 == 0, "icd_attention_probs_ex: acc must be 16-byte aligned");
+    ICD_CHECK_ARG(epi->first_cond_sample >= 0 && epi->first_cond_sample < B, "icd_attention_probs_ex: first_cond_sample out of range");
+    ICD_CHECK_ARG(!epi->edit_At || (epi->edit_D && Nk <= 80 && a.ldp <= 96),
+                  "icd_attention_probs_ex: the cross-attention edit needs edit_D, <= 80 keys and a base + >= 1 edited prompt");
+    const int b0 = probs_b0(a), groups = probs_groups(a);
+    ICD_CHECK_ARG(epi->first_cond_row % H == 0 && b0 < B, "icd_attention_probs_ex: first_cond_row must be a multiple of H inside the batch");
+    ICD_CHECK_ARG(!(epi->edit_At || epi->self_from_base) || B - b0 >= 2, "icd_attention_probs_ex: an edit needs a base prompt and at least one edited prompt");
+    ICD_CHECK_ARG(groups == 1 || epi->edit_count > 0, "icd_attention_probs_ex: group_count %d needs edit_count > 0", epi->group_count);
+    ICD_CHECK_ARG(groups > 1 || epi->edit_count <= 0 || epi->edit_count == B - b0 - 1,
+                  "icd_attention_probs_ex: edit_count %d does not match the %d edited samples of the launch", epi->edit_count, B - b0 - 1);
+    ICD_CHECK_ARG(groups == 1 || (long long)(B - b0) == (long long)groups * (epi->edit_count + 1),
+                  "icd_attention_probs_ex: %d conditional samples are not %d groups of %d prompts", B - b0, groups, epi->edit_count + 1);
+    return ICD_OK;
+}
+
+// epi: 0 no epilogue work, 1 acc / self_from_base, 2 the cross edit
+void probs_plan(int B, int H, int Nq, int d, int ldp, bool split, int epi, AttnPlan* p) {
+    *p = AttnPlan{};
+    p->family = ATTN_PROBS; p->variants = 40;
+    p->variant = 10 * (d <= 48 ? 0 : d <= 80 ? 1 : d <= 128 ? 2 : 3) + 5 * split + (epi == 2 ? 4 : 2 * epi + (ldp <= 96));
+    const ProbsRow& r = PROBS[p->variant];
+    p->KS = r.KS; p->SPLIT = r.SPLIT; p->EPI = r.EPI; p->FEW = r.FEW;
+    p->grid_x = (Nq + 127) / 128; p->grid_y = B * H; p->grid_z = 1;
+}
+int probs_epi_kind(const icd_probs_epilogue* e) { return !e ? 0 : e->edit_At ? 2 : (e->acc || e->self_from_base) ? 1 : 0; }
+
+template <int ROW>
+int probs_launch_row(const AttnPlan& p, const ProbsK& k, const ProbsEpi& ep, hipStream_t st) {
+    constexpr ProbsRow R = PROBS[ROW];
+    hipLaunchKernelGGL((attn_probs_kernel<R.KS, R.SPLIT, R.EPI, R.FEW>), dim3(p.grid_x, p.grid_y), dim3(256), 0, st, k, ep);
     ICD_CHECK_LAUNCH("icd_attention_probs");
     return ICD_OK;
 }
 
+}  // namespace
+
 extern "C" int icd_attention_probs(const void* q, const void* k, void* probs, int32_t B, int32_t H, int32_t Nq, int32_t Nk,
                                    int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale, void* stream) {
-    return attention_probs_run(q, nullptr, k, nullptr, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, stream);
+    return icd_attention_probs_ex(q, nullptr, k, nullptr, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, nullptr, stream);
 }
 
 extern "C" int icd_attention_probs_split(const void* q, const void* q_carry, const void* k, const void* k_carry, void* probs, int32_t B,
                                          int32_t H, int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale,
                                          void* stream) {
-    return attention_probs_run(q, q_carry, k, k_carry, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, stream);
+    return icd_attention_probs_ex(q, q_carry, k, k_carry, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, nullptr, stream);
 }
 
 extern "C" int icd_attention_probs_ex(const void* q, const void* q_carry, const void* k, const void* k_carry, void* probs, int32_t B,
                                       int32_t H, int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldp, float scale,
                                       const icd_probs_epilogue* epilogue, void* stream) {
-    return attention_probs_run(q, q_carry, k, k_carry, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, stream, epilogue);
+    const ProbsArgs a{q, q_carry, k, k_carry, probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale, epilogue};
+    const int rc = probs_validate(a);
+    if (rc != ICD_OK) return rc;
+    AttnPlan p;
+    probs_plan(B, H, Nq, d, ldp, q_carry || k_carry, probs_epi_kind(epilogue), &p);
+    const ProbsK kk{(const half_t*)q, (const half_t*)k, (half_t*)probs, B, H, Nq, Nk, d, ldq, ldk, ldp, scale * ATTN_LOG2E,
+                    (const unsigned char*)q_carry, (const unsigned char*)k_carry};
+    ProbsEpi ep{nullptr, nullptr, nullptr, 0, 0, 1};
+    if (epilogue) {
+        const int b0 = probs_b0(a);
+        ep = {(half_t*)epilogue->acc, (const half_t*)epilogue->edit_At, epilogue->edit_D, b0, epilogue->self_from_base != 0,
+              probs_groups(a) > 1 ? epilogue->edit_count + 1 : B - b0};
+    }
+    return attn_launch_row(p.variant, [&](auto row) { return probs_launch_row<decltype(row)::value>(p, kk, ep, (hipStream_t)stream); },
+                           std::make_index_sequence<40>{});
 }
 
 extern "C" int icd_attention_fused(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H,
@@ -1149,54 +1256,39 @@ extern "C" int icd_attention_fused(const void* q, const void* k, const void* vt,
 extern "C" int icd_attention_fused_ex(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H,
                                       int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
                                       int64_t vt_batch_stride, float scale, int32_t flags, void* stream) {
-    ICD_CHECK_ARG((flags & ~(ICD_ATTN_CAUSAL | ICD_ATTN_Q_PRESCALED | ICD_ATTN_TUNE_MODE0)) == 0, "icd_attention_fused: unknown flags 0x%x", flags);
-    ICD_CHECK_ARG(!(flags & ICD_ATTN_CAUSAL) || Nq == Nk, "icd_attention_fused: the causal mask needs Nq == Nk");
-    ICD_CHECK_ARG(scale > 0.f, "icd_attention_fused: scale must be positive");
-    ICD_CHECK_ARG(q && k && vt && out, "icd_attention_fused: null pointer");
-    ICD_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "icd_attention_fused: empty shape");
-    ICD_CHECK_ARG(d > 0 && d % 8 == 0 && d <= 160, "icd_attention_fused: head dim must be a multiple of 8, <= 160 (got %d)", d);
-    ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Nk,
-                  "icd_attention_fused: leading dims must be 16-byte aligned and ldvt >= Nk");
-    // (as icd_attention_masked: a sliced tensor with an odd element offset must be an error here, not a misaligned vector load there)
-    ICD_CHECK_ARG(ldq >= (long long)H * d && ldk >= (long long)H * d && ldo >= (long long)H * d, "icd_attention_fused: ldq, ldk and ldo must be >= H * d");
-    ICD_CHECK_ARG(vt_batch_stride == 0 || vt_batch_stride >= (int64_t)H * d * ldvt, "icd_attention_fused: vt_batch_stride below H * d * ldvt");
-    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) % 16 == 0 && (uintptr_t)out % 8 == 0,
-                  "icd_attention_fused: q, k and vt must be 16-byte aligned, out 8-byte");
-    AttnK a;
-    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.out = (half_t*)out;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
-    a.vt_bs = vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt;
-    const bool presc = (flags & ICD_ATTN_Q_PRESCALED) != 0;
-    a.scale_log2 = presc ? 1.0f : scale * ATTN_LOG2E;
-    // MODE 1 / 2 kernels (exponent offset subtracted by the MFMA); a causal mask has the fast form at head dim 64 only
-    const bool fast = presc && !(flags & ICD_ATTN_TUNE_MODE0) && (!(flags & ICD_ATTN_CAUSAL) || d == 64);
-    a.nqt = 0;
-    a.causal = (flags & ICD_ATTN_CAUSAL) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
-    // two query tiles per wave when the sequence is long enough to still fill the chip with 256-row workgroups
-    const bool wide = (long long)((Nq + 255) / 256) * B * H >= 512 && Nk >= 256 && !a.causal;
-    // cross-attention with enough query tiles to give every wave >= 2 of them (so the 24 KiB of K / V^T fragments per
-    // wave amortise and the next Q tile prefetches): K / V^T fragments live in registers.  Shorter problems (SDXL's
-    // 1024-query layers at batch 8) are launch + latency bound either way (~20 us for 42 MB) and stay on the tiled kernel.
-    if (Nk > 64 && Nk <= 96 && d <= 64 && !a.causal && (long long)((Nq + 127) / 128) * B * H >= 2048) {
-        if (d <= 32) return launch_attn_cross<2, 1>(a, st);
-        if (d <= 48) return launch_attn_cross<3, 2>(a, st);
-        return launch_attn_cross<4, 2>(a, st);
+    const AttnArgs a{q, k, vt, out, B, H, Nq, Nk, d, ldq, ldk, ldvt, ldo, vt_batch_stride, scale};
+    const int rc = fused_validate(a, flags);
+    if (rc != ICD_OK) return rc;
+    AttnPlan p;
+    fused_plan(B, H, Nq, Nk, d, flags, &p);
+    const AttnK kk{(const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, B, H, Nq, Nk, d, ldq, ldk, ldvt, ldo,
+                   vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt,
+                   (flags & ICD_ATTN_Q_PRESCALED) ? 1.0f : scale * ATTN_LOG2E,
+                   p.family == ATTN_TILED ? (Nq + 128 * p.QT - 1) / (128 * p.QT) : 0, (flags & ICD_ATTN_CAUSAL) ? 1 : 0};
+    return fused_launch(p, kk, (hipStream_t)stream);
+}
+
+// What the query does not hold stands in at a value no check refuses: an aligned non-null pointer (never dereferenced), scale 1, the
+// widest aligned leading dims, the default V^T stride, an epilogue of the asked kind with nothing else set.
+extern "C" int icd_attention_plan(const icd_attention_query* q, icd_attention_info* out) {
+    ICD_CHECK_ARG(q && out, "icd_attention_plan: null argument");
+    ICD_CHECK_ARG(q->entry >= 0 && q->entry <= 2, "icd_attention_plan: entry must be 0 (fused), 1 (probs) or 2 (masked), got %d", q->entry);
+    *out = icd_attention_info{};
+    void* const ptr = (void*)16;
+    constexpr int32_t LD = INT32_MAX - 7;
+    const AttnArgs a{ptr, ptr, ptr, ptr, q->B, q->H, q->Nq, q->Nk, q->d, LD, LD, LD, LD, 0, 1.0f};
+    if (q->entry == 2) return attn_masked_decide(a, (const int32_t*)ptr, out);
+    if (q->entry == 0) {
+        const int rc = fused_validate(a, q->flags);
+        if (rc == ICD_OK) fused_plan(q->B, q->H, q->Nq, q->Nk, q->d, q->flags, out);
+        return rc;
     }
-    if (d <= 16) return launch_attn<1, 1, 1, 2, 2>(a, st);
-    if (d <= 32) return launch_attn<2, 1, 1, 2, 2>(a, st);
-    // (round 3, same-box round-robin A/B at 4096 x 4096: one query tile per wave, three blocks per CU and a 3-stage ring are all
-    //  1 - 12 % slower than the configurations below with MODE 1 / 2; profiles/r03_attn_variants.txt)
-    if (fast && d == 40 && wide) return launch_attn<3, 2, 2, 2, 2, 1, 3>(a, st);       // P.V on 16-row tiles (48 rows, not 64)
-    if (fast && d == 40) return launch_attn<3, 2, 1, 2, 2, 1>(a, st);
-    if (fast && d == 64) return launch_attn<4, 2, 1, 2, 2, 2>(a, st);
-    if (fast && d == 80) return launch_attn<5, 3, 1, 2, 2, 2>(a, st);
-    if (d <= 48) return wide ? launch_attn<3, 2, 2, 2, 2>(a, st) : launch_attn<3, 2, 1, 2, 2>(a, st);
-    if (d <= 64) return launch_attn<4, 2, 1, 2, 2>(a, st);      // QT = 2 spills at d = 64 (measured slower)
-    if (d <= 80) return launch_attn<5, 3, 1, 2, 2>(a, st);
-    if (d <= 96) return launch_attn<6, 3, 1, 2, 2>(a, st);
-    if (d <= 128) return launch_attn<8, 4, 1, 2, 2>(a, st);
-    // head dim 160 (SD1.5's 16 x 16 / 8 x 8 levels): its accumulators and fragments do not fit the 256 registers of two waves per SIMD
-    // (187 spilt); one wave per SIMD with the whole register file is 10 - 35 % faster (profiles/r03_attn_small_kernels.txt)
-    return launch_attn<10, 5, 1, 1, 2>(a, st);
+    ICD_CHECK_ARG(q->epi >= 0 && q->epi <= 2, "icd_attention_plan: epi must be 0, 1 or 2, got %d", q->epi);
+    icd_probs_epilogue e{};
+    if (q->epi == 1) e.acc = ptr;
+    if (q->epi == 2) { e.edit_At = ptr; e.edit_D = (const float*)ptr; }
+    void* const carry = q->split ? ptr : nullptr;
+    const int rc = probs_validate(ProbsArgs{ptr, carry, ptr, carry, ptr, q->B, q->H, q->Nq, q->Nk, q->d, LD, LD, q->ldp, 1.0f, q->epi ? &e : nullptr});
+    if (rc == ICD_OK) probs_plan(q->B, q->H, q->Nq, q->d, q->ldp, q->split != 0, q->epi, out);
+    return rc;
 }

@@ -13,6 +13,7 @@
 //     0 * NaN is NaN).  No branch depends on the count.
 //   * the denominator sums the fp16-rounded probabilities the numerator uses; a count <= 0 has denominator 0 and writes zeros.
 #include "attn_frag.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -113,53 +114,56 @@ __global__ __launch_bounds__(64) void attn_masked_kernel(MaskedK p) {
     }
 }
 
-template <int NT, int DT>
-int launch_masked(const MaskedK& a, int B, hipStream_t st) {
-    hipLaunchKernelGGL((attn_masked_kernel<NT, DT>), dim3((a.Nq + 31) / 32, a.H, B), dim3(64), 0, st, a);
+struct MaskedRow { int NT, DT; };
+constexpr MaskedRow MASKED[16] = {{1, 1}, {1, 2}, {1, 3}, {1, 4}, {2, 1}, {2, 2}, {2, 3}, {2, 4},       // row = 4 (NT - 1) + DT - 1
+                                  {3, 1}, {3, 2}, {3, 3}, {3, 4}, {4, 1}, {4, 2}, {4, 3}, {4, 4}};
+
+int masked_validate(const AttnArgs& a, const int32_t* key_counts) {
+    ICD_CHECK_ARG(key_counts, "icd_attention_masked: key_counts is null");
+    ICD_CHECK_ARG(a.B <= 65535 && a.H <= 65535, "icd_attention_masked: B and H must be <= 65535");
+    if (a.d <= 0 || a.d % 8 != 0 || a.d > 128) {
+        icd_set_error("icd_attention_masked: head dim must be a multiple of 8, <= 128 (got %d)", a.d);
+        return ICD_ERR_UNSUPPORTED;
+    }
+    if (a.Nk > 128) {
+        icd_set_error("icd_attention_masked: at most 128 keys (got %d); longer rows go through icd_attention_fused", a.Nk);
+        return ICD_ERR_UNSUPPORTED;
+    }
+    ICD_CHECK_ARG((uintptr_t)key_counts % 4 == 0, "icd_attention_masked: q, k and vt must be 16-byte aligned, out 8-byte");
+    return attn_check_common("icd_attention_masked", a);
+}
+
+void masked_plan(int B, int H, int Nq, int Nk, int d, AttnPlan* p) {
+    *p = AttnPlan{};
+    p->family = ATTN_MASKED; p->variants = 16;
+    p->variant = 4 * (Nk <= 32 ? 0 : Nk <= 64 ? 1 : Nk <= 96 ? 2 : 3) + (d <= 32 ? 0 : d <= 64 ? 1 : d <= 96 ? 2 : 3);
+    p->NT = MASKED[p->variant].NT; p->DT = MASKED[p->variant].DT;
+    p->grid_x = (Nq + 31) / 32; p->grid_y = H; p->grid_z = B;
+}
+
+template <int ROW>
+int masked_launch_row(const AttnPlan& p, const MaskedK& k, hipStream_t st) {
+    hipLaunchKernelGGL((attn_masked_kernel<MASKED[ROW].NT, MASKED[ROW].DT>), dim3(p.grid_x, p.grid_y, p.grid_z), dim3(64), 0, st, k);
     ICD_CHECK_LAUNCH("icd_attention_masked");
     return ICD_OK;
 }
 
-template <int NT>
-int launch_masked_d(const MaskedK& a, int B, hipStream_t st) {
-    if (a.d <= 32) return launch_masked<NT, 1>(a, B, st);
-    if (a.d <= 64) return launch_masked<NT, 2>(a, B, st);
-    if (a.d <= 96) return launch_masked<NT, 3>(a, B, st);
-    return launch_masked<NT, 4>(a, B, st);
-}
-
 }  // namespace
+
+int attn_masked_decide(const AttnArgs& a, const int32_t* key_counts, AttnPlan* p) {
+    const int rc = masked_validate(a, key_counts);
+    if (rc == ICD_OK) masked_plan(a.B, a.H, a.Nq, a.Nk, a.d, p);
+    return rc;
+}
 
 extern "C" int icd_attention_masked(const void* q, const void* k, const void* vt, void* out, const int32_t* key_counts, int32_t B,
                                     int32_t H, int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
                                     int64_t vt_batch_stride, float scale, void* stream) {
-    ICD_CHECK_ARG(q && k && vt && out, "icd_attention_masked: null pointer");
-    ICD_CHECK_ARG(key_counts, "icd_attention_masked: key_counts is null");
-    ICD_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "icd_attention_masked: empty shape");
-    ICD_CHECK_ARG(B <= 65535 && H <= 65535, "icd_attention_masked: B and H must be <= 65535");
-    ICD_CHECK_ARG(scale > 0.f, "icd_attention_masked: scale must be positive");
-    if (d <= 0 || d % 8 != 0 || d > 128) {
-        icd_set_error("icd_attention_masked: head dim must be a multiple of 8, <= 128 (got %d)", d);
-        return ICD_ERR_UNSUPPORTED;
-    }
-    if (Nk > 128) {
-        icd_set_error("icd_attention_masked: at most 128 keys (got %d); longer rows go through icd_attention_fused", Nk);
-        return ICD_ERR_UNSUPPORTED;
-    }
-    ICD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Nk,
-                  "icd_attention_masked: leading dims must be 16-byte aligned and ldvt >= Nk");
-    ICD_CHECK_ARG(ldq >= H * d && ldk >= H * d && ldo >= H * d, "icd_attention_masked: ldq, ldk and ldo must be >= H * d");
-    ICD_CHECK_ARG(vt_batch_stride == 0 || vt_batch_stride >= (int64_t)H * d * ldvt, "icd_attention_masked: vt_batch_stride below H * d * ldvt");
-    ICD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) % 16 == 0 && (uintptr_t)out % 8 == 0 && (uintptr_t)key_counts % 4 == 0,
-                  "icd_attention_masked: q, k and vt must be 16-byte aligned, out 8-byte");
-    MaskedK a;
-    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.out = (half_t*)out; a.counts = key_counts;
-    a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
-    a.vt_bs = vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt;
-    a.scale_log2 = scale * ATTN_LOG2E;
-    hipStream_t st = (hipStream_t)stream;
-    if (Nk <= 32) return launch_masked_d<1>(a, B, st);
-    if (Nk <= 64) return launch_masked_d<2>(a, B, st);
-    if (Nk <= 96) return launch_masked_d<3>(a, B, st);
-    return launch_masked_d<4>(a, B, st);
+    AttnPlan p;
+    const int rc = attn_masked_decide(AttnArgs{q, k, vt, out, B, H, Nq, Nk, d, ldq, ldk, ldvt, ldo, vt_batch_stride, scale}, key_counts, &p);
+    if (rc != ICD_OK) return rc;
+    const MaskedK kk{(const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, key_counts, H, Nq, Nk, d, ldq, ldk, ldvt, ldo,
+                     vt_batch_stride > 0 ? vt_batch_stride : (long long)H * d * ldvt, scale * ATTN_LOG2E};
+    return attn_launch_row(p.variant, [&](auto row) { return masked_launch_row<decltype(row)::value>(p, kk, (hipStream_t)stream); },
+                           std::make_index_sequence<16>{});
 }

@@ -1,7 +1,8 @@
 """CPU companion of test_attn_edges_gpu.py: the case tables of the attention entries' edge tests (icd_attention_fused_ex,
-icd_attention_probs*, csrc/attention.hip), the instantiation each case is meant to take (a pure-Python copy of the host dispatch, pinned
-against the source text), the per-element error bounds the GPU tests assert - established here on the reference alone - and the argument
-refusals of the entries, which all happen before any HIP call.
+icd_attention_probs*, csrc/attention.hip), the instantiation each case is meant to take (a pure-Python copy of the host dispatch - written
+when the dispatch was an `if` ladder and then pinned against its source text, unchanged since - held against what icd_attention_plan
+answers), the per-element error bounds the GPU tests assert - established here on the reference alone - and the argument refusals of the
+entries, which all happen before any HIP call.
 
 The bounds.  u = 2^-23 (a whole fp32 ulp: neither the MFMA's internal rounding nor v_exp_f32's accuracy has been measured on this chip),
 c = scale * log2(e) (1 for a prescaled q), A = max_j c * sum_i |q_i| |k_ji| over the keys the row may see (the size of a base-2 exponent's
@@ -33,8 +34,6 @@ first two samples' first three heads.  The GPU tests assert the kernels against 
 """
 import ctypes as C
 import math
-import os
-import re
 
 import pytest
 import torch
@@ -50,7 +49,6 @@ LN2 = math.log(2.0)
 LOG2E = 1.0 / LN2
 INF = float("inf")
 CAUSAL, PRESC, MODE0 = 1, 2, 4                     # ICD_ATTN_CAUSAL, ICD_ATTN_Q_PRESCALED, ICD_ATTN_TUNE_MODE0
-SRC = os.path.join(os.path.dirname(_lib.__file__), "csrc", "attention.hip")
 
 
 def cdiv(a, b):
@@ -106,6 +104,43 @@ def probs_dispatch(d, ldp, split=False, epi=0):
     """attention_probs_run's choice: (KS, SPLIT, EPI, FEW); epi 0 none, 1 acc / self replacement, 2 the cross edit (few keys only)."""
     ks = 3 if d <= 48 else 5 if d <= 80 else 8 if d <= 128 else 10
     return (ks, split, epi, True if epi == 2 else ldp <= 96)
+
+
+def masked_dispatch(Nk, d):
+    """icd_attention_masked's choice: (NT, DT), 32-key tiles and 32-row tiles of the head dim."""
+    tiles = lambda n: 1 if n <= 32 else 2 if n <= 64 else 3 if n <= 96 else 4
+    return tiles(Nk), tiles(d)
+
+
+def plan(entry, B, H, Nq, Nk, d, ldp=0, flags=0, split=False, epi=0):
+    """icd_attention_plan (entry 0 fused, 1 probs, 2 masked): (status, icd_attention_info)"""
+    query, info = _lib.AttentionQuery(entry, B, H, Nq, Nk, d, ldp, flags, int(split), epi), _lib.AttentionInfo()
+    return _lib.load().icd_attention_plan(C.byref(query), C.byref(info)), info
+
+
+def plan_fused(B, H, Nq, Nk, d, flags=0):
+    """The library's answer in the mirror's terms: (what fused_dispatch returns, what cross_plan returns or None, info); the fields the
+    mirror leaves out (OCC, NST, grid, LDS ring) are asserted here."""
+    rc, i = plan(0, B, H, Nq, Nk, d, flags=flags)
+    assert rc == 0 and i.variants == (22, 6)[i.family] and (i.grid_y, i.grid_z) == (1, 1)
+    if i.family == 1:
+        assert i.grid_x == cdiv(Nq, 128 * i.tiles_per_wave) * B * H and i.lds_bytes == 0
+        return ("cross", i.KS, i.DT, 1, 0, 0, False), (i.tiles_per_wave, i.STL), i
+    assert (i.OCC, i.NST) == (1 if i.KS == 10 else 2, 2) and i.grid_x == cdiv(Nq, 128 * i.QT) * B * H
+    assert i.lds_bytes == i.NST * (64 * 32 * i.KS + (16 * i.DR if i.DR else 32 * i.DT) * 128)
+    return ("tiled", i.KS, i.DT, i.QT, i.MODE, i.DR, bool(i.causal)), None, i
+
+
+def plan_probs(r):
+    rc, i = plan(1, r["B"], r["H"], r["Nq"], r["Nk"], r["d"], r["ldp"], split=r["split"], epi=r["epi"])
+    assert rc == 0 and (i.family, i.variants) == (2, 40) and (i.grid_x, i.grid_y, i.grid_z, i.lds_bytes) == (cdiv(r["Nq"], 128), r["B"] * r["H"], 1, 0)
+    return (i.KS, bool(i.SPLIT), i.EPI, bool(i.FEW)), i
+
+
+def plan_masked(B, H, Nq, Nk, d):
+    rc, i = plan(2, B, H, Nq, Nk, d)
+    assert rc == 0 and (i.family, i.variants) == (3, 16) and (i.grid_x, i.grid_y, i.grid_z, i.lds_bytes) == (cdiv(Nq, 32), H, B, 0)
+    return (i.NT, i.DT), i
 
 
 # ============================================================================================================ 1. case tables
@@ -340,71 +375,65 @@ def scale_of(r):
 def test_every_row_takes_the_instantiation_it_is_there_for():
     for rows in FUSED_TABLES.values():
         for r in rows:
-            assert fused_dispatch(r["B"], r["H"], r["Nq"], r["Nk"], r["d"], r["flags"]) == r["want"], r
+            got, got_cross, _ = plan_fused(r["B"], r["H"], r["Nq"], r["Nk"], r["d"], r["flags"])
+            assert fused_dispatch(r["B"], r["H"], r["Nq"], r["Nk"], r["d"], r["flags"]) == r["want"] == got, r
             if r["want"][0] == "cross":
-                assert cross_plan(r["B"], r["H"], r["Nq"], r["Nk"]) == r["cross"], r
+                assert cross_plan(r["B"], r["H"], r["Nq"], r["Nk"]) == r["cross"] == got_cross, r
     for r in G_ROWS:
-        assert probs_dispatch(r["d"], r["ldp"], r["split"], r["epi"]) == r["want"], r
+        assert probs_dispatch(r["d"], r["ldp"], r["split"], r["epi"]) == r["want"] == plan_probs(r)[0], r
         assert r["ldp"] % 8 == 0 and r["ldp"] >= r["Nk"]
+    for r in H_ROWS:
+        assert masked_dispatch(r["Nk"], r["d"]) == plan_masked(r["B"], r["H"], r["Nq"], r["Nk"], r["d"])[0], r
     # the wide rows are the smallest that reach the wide kernels, the cross rows sit on the threshold
     assert all(cdiv(r["Nq"], 256) * r["B"] * r["H"] == 512 for r in D_ROWS) and all(r["B"] * r["H"] == 2048 for r in E_ROWS)
 
 
-def _source_instantiations():
-    """The instantiations the dispatcher's text can reach: every launch_attn<...> of icd_attention_fused_ex (+ its causal twin where
-    launch_attn has one), every launch_attn_cross<KS, DT> with both STL, every attn_probs_kernel<KS, SP, EP, FW> of ICD_PROBS / ICD_PROBS2."""
-    src = open(SRC).read()
-    body = src[src.rindex('extern "C" int icd_attention_fused_ex'):]
-    fused = set()
-    for args in re.findall(r"launch_attn<([0-9, ]+)>\(a, st\)", body):
-        a = [int(x) for x in args.split(",")] + [0, 0]
-        ks, dt, qt, mode, dr = a[0], a[1], a[2], a[5], a[6]            # <KS, DT, QT, OCC, NST, MODE = 0, DR = 0>
-        fused.add(("tiled", ks, dt, qt, mode, dr, False))
-        if qt == 1 and (mode == 0 or (mode == 2 and ks == 4)):             # launch_attn's `if constexpr`
-            fused.add(("tiled", ks, dt, qt, mode, 0, True))
-    cross = {("cross", int(a), int(b), stl) for a, b in re.findall(r"launch_attn_cross<(\d+), (\d+)>\(a, st\)", body) for stl in (5, 6)}
-    ks_probs = [int(x) for x in re.findall(r"attn_probs_kernel<(\d+), SP, EP, FW>", src)]
-    probs = {(ks, sp, ep, fw) for ks in ks_probs for sp in (False, True) for ep, fws in ((0, (False, True)), (1, (False, True)), (2, (True,)))
-             for fw in fws}
-    return src, fused, cross, probs
+# Shapes (B, H, Nq, Nk) of the fused sweep: one per regime (plain, causal-capable, wide, cross with both STL), then both sides of every
+# threshold of the dispatch.  wide: ceil(Nq / 256) B H = 511 | 512, and Nk = 255 | 256 at 512 blocks (Nq == Nk there: a causal call must
+# stay narrow).  cross: ceil(Nq / 128) B H = 2047 | 2048 at the key counts either side of 64 | 65, 80 | 81 (STL), 96 | 97, crossed with
+# every head dim (32 | 40, 48 | 56, 64 | 72 among them); 2048 blocks with Nq == Nk (a causal call must stay on the tiled kernel).
+# Tiles per wave: ceil(Nq / (128 tpw)) B H = 1023 | 1024 for tpw = 8, 4, 2, 1 - below 1024 blocks at tpw = 2 the cross rule itself
+# (2048 blocks of 128 rows) cannot hold, so one tile per wave is out of reach and the last three shapes run tiled.
+SWEEP_SHAPES = [(2, 2, 100, 77), (2, 2, 100, 100), (4, 64, 300, 256), (32, 64, 100, 77), (32, 64, 100, 96),
+                (1, 511, 256, 256), (1, 512, 256, 256), (1, 512, 256, 255), (1, 2048, 77, 77)] + \
+               [(1, bh, 128, Nk) for bh in (2047, 2048) for Nk in (64, 65, 80, 81, 96, 97)] + \
+               [(1, 1023, 1024, 77), (1, 1024, 1024, 77), (1, 341, 1536, 77), (1, 512, 1024, 77), (1, 341, 768, 77), (1, 256, 1024, 77),
+                (1, 1023, 128, 77), (1, 128, 1024, 77)]
 
 
-def test_the_mirror_agrees_with_the_dispatcher_source_and_the_tables_reach_everything():
-    src, fused, cross, probs = _source_instantiations()
-    # the thresholds, as the source writes them
-    for text in ("if (d <= 16) return launch_attn<1, 1, 1, 2, 2>", "if (d <= 32) return launch_attn<2, 1, 1, 2, 2>", "if (d <= 48) return wide ?",
-                 "if (d <= 64) return launch_attn<4, 2, 1, 2, 2>", "if (d <= 80) return launch_attn<5, 3, 1, 2, 2>",
-                 "if (d <= 96) return launch_attn<6, 3, 1, 2, 2>", "if (d <= 128) return launch_attn<8, 4, 1, 2, 2>",
-                 "return launch_attn<10, 5, 1, 1, 2>", "Nk > 64 && Nk <= 96 && d <= 64 && !a.causal && (long long)((Nq + 127) / 128) * B * H >= 2048",
-                 "(long long)((Nq + 255) / 256) * B * H >= 512 && Nk >= 256 && !a.causal", "if (d <= 32) return launch_attn_cross<2, 1>",
-                 "if (d <= 48) return launch_attn_cross<3, 2>", "return launch_attn_cross<4, 2>", "fast && d == 40 && wide", "fast && d == 40)",
-                 "fast && d == 64)", "fast && d == 80)", "(!(flags & ICD_ATTN_CAUSAL) || d == 64)", "if (k.Nk <= 80)", "int tpw = 8;",
-                 "* k.B * k.H < 1024) tpw >>= 1", "if (ldp <= 96) ICD_PROBS(SP, EP, true); else ICD_PROBS(SP, EP, false)",
-                 "if (d <= 48) hipLaunchKernelGGL((attn_probs_kernel<3,", "else if (d <= 80) hipLaunchKernelGGL((attn_probs_kernel<5,",
-                 "else if (d <= 128) hipLaunchKernelGGL((attn_probs_kernel<8,", "else hipLaunchKernelGGL((attn_probs_kernel<10,",
-                 "if (ep.At) ICD_PROBS(true, 2, true)", "if (ep.At) ICD_PROBS(false, 2, true)"):
-        assert text in src, text
-    # what the mirror can reach, over every head dim, flag set and one shape per regime (plain, wide, cross with both STL)
-    shapes = [(2, 2, 100, 77), (2, 2, 100, 100), (4, 64, 300, 256), (32, 64, 100, 77), (32, 64, 100, 96)]
-    reach_f, reach_c = set(), set()
+def test_the_mirror_agrees_with_the_library_and_the_tables_reach_everything():
+    seen = {0: set(), 1: set(), 2: {}, 3: set()}                           # family -> variants the sweep reached (probs: variant -> EPI)
+    tpws = set()
     for d in range(8, 161, 8):
         for flags in (0, PRESC, PRESC | MODE0, CAUSAL, CAUSAL | PRESC, CAUSAL | PRESC | MODE0):
-            for B, H, Nq, Nk in shapes:
+            for B, H, Nq, Nk in SWEEP_SHAPES:
                 if (flags & CAUSAL) and Nq != Nk:
                     continue
-                t = fused_dispatch(B, H, Nq, Nk, d, flags)
-                if t[0] == "cross":
-                    reach_c.add(t[:3] + (cross_plan(B, H, Nq, Nk)[1],))
-                else:
-                    reach_f.add(t)
-    reach_p = {probs_dispatch(d, ldp, sp, ep) for d in range(8, 161, 8) for ldp in (96, 104) for sp in (False, True) for ep in (0, 1, 2)}
-    assert reach_f == fused and reach_c == cross and reach_p == probs
-    assert len(fused) == 22 and len(cross) == 6 and len(probs) == 40
+                got, got_cross, i = plan_fused(B, H, Nq, Nk, d, flags)
+                assert got == fused_dispatch(B, H, Nq, Nk, d, flags), (B, H, Nq, Nk, d, flags)
+                assert got_cross is None or got_cross == cross_plan(B, H, Nq, Nk), (B, H, Nq, Nk, d)
+                seen[i.family].add(i.variant)
+                tpws.add(i.tiles_per_wave)
+        for ldp in (88, 96, 104):
+            for sp in (False, True):
+                for ep in (0, 1, 2):
+                    r = dict(B=3, H=2, Nq=100, Nk=77, d=d, ldp=ldp, split=sp, epi=ep)
+                    if ep == 2 and ldp > 96:                               # the cross edit exists for <= 96 columns only
+                        assert plan(1, 3, 2, 100, 77, d, ldp, split=sp, epi=2)[0] == -1
+                        continue
+                    got, i = plan_probs(r)
+                    assert got == probs_dispatch(d, ldp, sp, ep), r
+                    seen[2][i.variant] = i.EPI
+        for Nk in (1, 32, 33, 64, 65, 96, 97, 128) if d <= 128 else ():
+            got, i = plan_masked(2, 3, 100, Nk, d)
+            assert got == masked_dispatch(Nk, d), (Nk, d)
+            seen[3].add(i.variant)
+    assert tpws == {0, 8, 4, 2}                                            # (0: the tiled kernel)
+    assert [sorted(seen[f]) for f in range(4)] == [list(range(n)) for n in (22, 6, 40, 16)]
     # ... and the tables hit all of it (the cross-edit instantiations, EPI = 2, keep their bit-for-bit tests in test_ops_gpu.py / test_p2p_gpu.py)
-    rows = [r for t in FUSED_TABLES.values() for r in t]
-    assert {r["want"] for r in rows if r["want"][0] == "tiled"} == fused
-    assert {r["want"][:3] + (r["cross"][1],) for r in rows if r["want"][0] == "cross"} == cross
-    assert {r["want"] for r in G_ROWS} == {p for p in probs if p[2] != 2}
+    rows = [plan_fused(r["B"], r["H"], r["Nq"], r["Nk"], r["d"], r["flags"])[2] for t in FUSED_TABLES.values() for r in t]
+    assert [{i.variant for i in rows if i.family == f} for f in (0, 1)] == [seen[0], seen[1]]
+    assert {plan_probs(r)[1].variant for r in G_ROWS} == {v for v, epi in seen[2].items() if epi != 2}
 
 
 @pytest.mark.parametrize("sec", list(FUSED_TABLES))
@@ -546,3 +575,32 @@ def test_attention_probs_refuses(name, entry, epi, kw, fragment):
     lib = _lib.load()
     assert _probs(entry, _epi(**epi) if epi is not None else None, **kw) == -1, name
     assert fragment.encode() in lib.icd_last_error(), (name, lib.icd_last_error())
+
+
+_Q = dict(B=3, H=2, Nq=35, Nk=35, d=64, ldp=40)
+PLAN_REFUSALS = [                                  # what the entries refuse on shape and flags alone, with their status and message
+    ("fused d = 12", 0, dict(d=12), -1, "head dim"), ("fused d = 168", 0, dict(d=168), -1, "head dim"),
+    ("fused unknown flags", 0, dict(flags=8), -1, "unknown flags"), ("fused causal Nq != Nk", 0, dict(flags=CAUSAL, Nq=36), -1, "Nq == Nk"),
+    ("masked Nk = 129", 2, dict(Nk=129), -2, "128 keys"), ("masked d = 136", 2, dict(d=136), -2, "head dim"),
+    ("masked d = 36", 2, dict(d=36), -2, "head dim"),
+    ("probs d = 12", 1, dict(d=12), -1, "head dim"), ("probs d = 168", 1, dict(d=168), -1, "head dim"),
+    ("probs ldp < Nk", 1, dict(ldp=32), -1, "ldp >= Nk"), ("probs ldp % 8", 1, dict(ldp=44), -1, "ldp >= Nk"),
+    ("probs edit with 81 keys", 1, dict(epi=2, Nk=81, ldp=88), -1, "the cross-attention edit needs edit_D"),
+    ("probs edit with ldp 104", 1, dict(epi=2, ldp=104), -1, "the cross-attention edit needs edit_D"),
+    ("probs grid limit", 1, dict(B=32768), -1, "grid limit"),
+]
+
+
+@pytest.mark.parametrize("name,entry,kw,status,fragment", PLAN_REFUSALS, ids=[r[0] for r in PLAN_REFUSALS])
+def test_attention_plan_refuses_what_the_entry_refuses(name, entry, kw, status, fragment):
+    assert plan(entry, **dict(_Q, **kw))[0] == status, name
+    assert fragment.encode() in _lib.load().icd_last_error(), (name, _lib.load().icd_last_error())
+
+
+def test_attention_plan_accepts_what_only_a_pointer_refuses():
+    lib = _lib.load()
+    assert _fused(q=None) == -1 and _fused(out=P0 + 4) == -1 and plan(0, 2, 2, 35, 35, 64)[0] == 0
+    assert _probs(q=None) == -1 and _probs("split", kc=P0 + 1) == -1 and plan(1, 3, 2, 35, 35, 64, 40, split=True)[0] == 0
+    assert _probs("ex", _epi(acc=P0 + 8)) == -1 and plan(1, 3, 2, 35, 35, 64, 40, split=True, epi=1)[0] == 0
+    assert lib.icd_attention_masked(P0, P0, P0, P0, None, 2, 2, 35, 35, 64, 128, 128, 40, 128, 0, 0.125, None) == -1
+    assert plan(2, 2, 2, 35, 35, 64)[0] == 0

@@ -88,7 +88,8 @@ def test_header_is_plain_c_and_the_ctypes_mirrors_have_its_layout(tmp_path):
     gcc = shutil.which("gcc")
     if gcc is None:
         pytest.skip("no C compiler on this box")
-    pairs = {"icd_gemm_desc": _lib.GemmDesc, "icd_gemm_plan_info": _lib.GemmPlanInfo, "icd_unet_config": _lib.UNetConfig, "icd_unet_io": _lib.UNetIO}
+    pairs = {"icd_gemm_desc": _lib.GemmDesc, "icd_gemm_plan_info": _lib.GemmPlanInfo, "icd_unet_config": _lib.UNetConfig, "icd_unet_io": _lib.UNetIO,
+             "icd_attention_query": _lib.AttentionQuery, "icd_attention_info": _lib.AttentionInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "icd_amd.h"', "int main(void) {"]
     for cname, cls in pairs.items():
         lines.append(f'  printf("{cname} size %zu\\n", sizeof({cname}));')
