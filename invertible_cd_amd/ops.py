@@ -457,9 +457,13 @@ def silu(x):
     return out
 
 
+def p2p_cross_edit_geometry(nk, ld):    # rows of icd_p2p_cross_edit_groups and the probability kernel's edit epilogue: 80 columns
+    return nk <= 80 and ld >= 80 and ld % 8 == 0
+
+
 def p2p_cross_edit_supported(probs):
-    return (probs.is_cuda and probs.dtype == torch.float16 and probs.dim() == 3 and probs.stride(2) == 1 and probs.shape[2] <= 80
-            and probs.stride(1) >= 80 and probs.stride(1) % 8 == 0 and probs.stride(0) == probs.shape[1] * probs.stride(1)
+    return (probs.is_cuda and probs.dtype == torch.float16 and probs.dim() == 3 and probs.stride(2) == 1
+            and p2p_cross_edit_geometry(probs.shape[2], probs.stride(1)) and probs.stride(0) == probs.shape[1] * probs.stride(1)
             and probs.data_ptr() % 16 == 0)
 
 
@@ -474,20 +478,14 @@ def p2p_pack_operator(A, D):
 
 
 def p2p_cross_edit(probs, n_prompts, At, Dp):
-    """In place on the conditional rows of one cross-attention module: probs fp16 [n_prompts*heads, nq, nk <= 80], a view
-    with row stride ld >= 80 (pad columns zero) of a contiguous buffer; (At, Dp) from p2p_pack_operator."""
-    assert p2p_cross_edit_supported(probs)
-    bh, nq, nk = probs.shape
-    assert bh % n_prompts == 0 and tuple(At.shape) == (n_prompts - 1, 96, 80) and tuple(Dp.shape) == (n_prompts - 1, 96)
-    assert At.dtype == torch.float16 and At.is_contiguous() and Dp.dtype == torch.float32 and Dp.is_contiguous()
-    _lib.check(_lib.load().icd_p2p_cross_edit(_p(probs), n_prompts, bh // n_prompts, nq, nk, probs.stride(1), _p(At), _p(Dp),
-                                              _stream()), "icd_p2p_cross_edit")
-    return probs
+    """p2p_cross_edit_groups for one prompt group."""
+    return p2p_cross_edit_groups(probs, 1, n_prompts, At, Dp)
 
 
 def p2p_cross_edit_groups(probs, n_groups, n_prompts, At, Dp):
-    """p2p_cross_edit for n_groups independent prompt groups in one launch (icd_p2p_cross_edit_groups): probs fp16
-    [n_groups*n_prompts*heads, nq, nk <= 80] group-major, (At, Dp) the groups' packed operators concatenated
+    """In place on the conditional rows of one cross-attention module, n_groups independent prompt groups in one launch
+    (icd_p2p_cross_edit_groups): probs fp16 [n_groups*n_prompts*heads, nq, nk <= 80] group-major, a view with row stride ld >= 80 (pad
+    columns zero) of a contiguous buffer; (At, Dp) the groups' packed operators (p2p_pack_operator) concatenated
     ([n_groups*(n_prompts-1), 96, 80] / [n_groups*(n_prompts-1), 96])."""
     assert p2p_cross_edit_supported(probs)
     bh, nq, nk = probs.shape

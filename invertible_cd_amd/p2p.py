@@ -16,6 +16,16 @@ probabilities must be materialised at all:
     when w_embed_dim > 0) the controller's `forward` - which in the reference only ever sees the conditional half,
     utils/p2p.py:106-107 - is applied to the whole (cond-only) tensor.  The SDXL sampler (generation_sdxl.sample_deterministic
     with `controller=`) always runs this layout: its batch [source, edit_1, ...] has no unconditional half at all.
+
+Who decides what on a materialised layer.  The controller says what it needs: every editing controller is a `PromptGroupEdit`, G prompt
+groups of P on the conditional samples (`layout`: one reference-shaped controller is (1, P), a `ControllerBatch` (G, P)), with a step's
+packed cross-attention operators (`cross_edit_operator`), its self-replace window (`self_window`) and, as an AttentionStore, the store
+tensor that the layer's map goes to (`store_target`).  The adapter plans (`HookAdapter.plan`, written once, for G groups) which of these
+the probability kernel's epilogue takes over for this batch layout and layer geometry: one pass over P instead of three
+(`controller.fused_epilogue = False`, `controller.cond_rows_only = False`: the A/B switches, same bits).  The kernel executes.  The
+`LayerCall` record carries the plan from `query` to `probs_ready`, which tells the controller what is already done (`kernel_did`):
+`forward` leaves that edit alone and `between_steps` skips those entries.  The rest runs as one launch for all groups where the rows
+are the kernel's (`PromptGroupEdit.edit_rows`, `LocalBlend.blend_groups`), else as the torch expressions that the goldens pin.
 """
 import abc
 from typing import Dict, List, Optional, Tuple, Union
@@ -48,6 +58,7 @@ class LocalBlend:
         self.start_blend = int(start_blend * NUM_DDIM_STEPS)
         self.counter = 0
         self.th = th
+        self._device_terms = {}        # blend_groups' cache for this LocalBlend alone
 
     @staticmethod
     def _word_mask(prompts, words):
@@ -102,23 +113,39 @@ class LocalBlend:
     def __call__(self, x_t, attention_store):
         """`x_t[e] <- x_t[0] + mask[e] * (x_t[e] - x_t[0])` from the accumulated quarter-side cross-attention maps
         (utils/p2p.py:33-44: down_cross[2:4] + up_cross[:3] at 16 x 16)."""
+        return self.blend(x_t, attention_store) if self.due() else x_t
+
+    def due(self):                                               # advance the step counter: is this step past start_blend?
         self.counter += 1
-        if self.counter <= self.start_blend:
-            return x_t
-        return self.blend(x_t, attention_store)
+        return self.counter > self.start_blend
+
+    @staticmethod
+    def blend_groups(lbs, active, x_t, layers, side, cache):
+        """The blend of G prompt groups (`lbs`: a LocalBlend or None each, a lone LocalBlend is the one-element list; `active`: which of
+        them blend at this step) in two HIP launches: word-weighted mean of the maps; pool, normalise, threshold, OR with the base prompt's
+        mask, substruct words, nearest resize and the blend itself.  None where the torch expression has to run.  `cache`: the caller's."""
+        P = x_t.shape[0] // len(lbs)
+        if not (LocalBlend._on_device(x_t, layers, side) and all(lb is None or lb.alpha_layers.shape[0] == P for lb in lbs)):
+            return None
+        dev = x_t.device
+        if str(dev) not in cache:
+            def words(mask):                                     # a group's [P, 77] word mask; zero where it has none
+                return torch.zeros(P, MAX_NUM_WORDS, device=dev) if mask is None else mask.reshape(P, MAX_NUM_WORDS).to(dev, torch.float32)
+            has_sub = [lb is not None and lb.substruct_layers is not None for lb in lbs]
+            sub = (torch.cat([words(lb.substruct_layers if h else None) for lb, h in zip(lbs, has_sub)]), has_sub) if any(has_sub) else None
+            cache[str(dev)] = (torch.cat([words(None if lb is None else lb.alpha_layers) for lb in lbs]), sub,
+                               [0.0 if lb is None else lb.th[0] for lb in lbs], [0.0 if lb is None else lb.th[1] for lb in lbs])
+        alpha, sub, th_pool, th_sub = cache[str(dev)]
+        from . import ops
+        return ops.local_blend_groups(layers, alpha, sub, th_pool, th_sub, active, x_t.contiguous(), len(lbs), res=side[0])
 
     def blend(self, x_t, attention_store):
         """The blend itself, past start_blend (what __call__ does after advancing its counter)."""
-        n_prompts = self.alpha_layers.shape[0]
         layers, side = self.select_maps(attention_store, x_t)
-        if self._on_device(x_t, layers, side):
-            # two HIP launches (icd_local_blend_groups_ws): word-weighted mean of the maps; pool, normalise, threshold, OR with the
-            # base prompt's mask, substruct words, nearest resize and the blend itself
-            from . import ops
-            sub = None if self.substruct_layers is None else self.substruct_layers.reshape(n_prompts, MAX_NUM_WORDS)
-            return ops.local_blend(layers, self.alpha_layers.reshape(n_prompts, MAX_NUM_WORDS), sub, self.th[0], self.th[1],
-                                   x_t.contiguous(), res=side[0])
-        maps = torch.cat([m.reshape(n_prompts, -1, 1, side[0], side[1], MAX_NUM_WORDS) for m in layers], dim=1)
+        out = self.blend_groups([self], [True], x_t, layers, side, self._device_terms)
+        if out is not None:
+            return out
+        maps = torch.cat([m.reshape(self.alpha_layers.shape[0], -1, 1, side[0], side[1], MAX_NUM_WORDS) for m in layers], dim=1)
         mask = self.get_mask(maps, self.alpha_layers, True, x_t)
         if self.substruct_layers is not None:
             mask = mask * ~self.get_mask(maps, self.substruct_layers, False, x_t)
@@ -224,14 +251,17 @@ class AttentionStore(AttentionControl):
         super().__init__()
         self.step_store = self.get_empty_store()
         self.attention_store = {}
-        self._fused_acc = set()        # (key, index) of this step's maps the probability kernel has already added to attention_store
+        self.layout = None             # (G, P): the rows are G prompt groups of P that an edit couples (PromptGroupEdit); None: only stored
+        self.kernel_edit = False       # kernel_did: the probability kernel has applied this step's edit to the layer being handed over
+        self._fused_acc = set()        # kernel_did: (key, index) of this step's maps the probability kernel has added to attention_store
+        self._acc_geometry = {}        # store_target: (key, index) -> (store tensor, can the kernel add to it), checked once per tensor
 
     @staticmethod
     def get_empty_store():
         return {f"{place}_{kind}": [] for kind in ("cross", "self") for place in ("down", "mid", "up")}
 
     def needs_probs(self, is_cross, n_queries, place_in_unet):
-        return n_queries <= self.STORE_MAX_QUERIES
+        return (self.layout is not None and is_cross) or n_queries <= self.STORE_MAX_QUERIES
 
     def forward(self, attn, is_cross: bool, place_in_unet: str):
         if attn.shape[1] <= self.STORE_MAX_QUERIES:
@@ -242,9 +272,8 @@ class AttentionStore(AttentionControl):
         if not self.attention_store:
             self.attention_store = self.step_store
         else:
-            fused = self._fused_acc            # added by the probability kernel's epilogue (HookAdapter, icd_probs_epilogue.acc)
             pairs = [(t, self.step_store[key][i]) for key, acc in self.attention_store.items() for i, t in enumerate(acc)
-                     if (key, i) not in fused]
+                     if (key, i) not in self._fused_acc]       # those the probability kernel's epilogue has added (icd_probs_epilogue.acc)
             if pairs and all(t.is_cuda and t.dtype == torch.float16 and t.is_contiguous() and s.is_cuda and s.dtype == torch.float16
                              and s.is_contiguous() and t.shape == s.shape and t.data_ptr() % 16 == 0 and s.data_ptr() % 16 == 0
                              for t, s in pairs):
@@ -259,28 +288,82 @@ class AttentionStore(AttentionControl):
     def get_average_attention(self):
         return {key: [t / self.cur_step for t in ts] for key, ts in self.attention_store.items()}
 
+    def store_target(self, key, shape, ld):
+        """(index, tensor) of attention_store that the next map of `key` is added to, where the probability kernel can do that itself
+        (fp16 on the GPU, `shape` with rows of `ld`, 16-byte aligned); else None: between_steps adds it."""
+        idx = len(self.step_store[key])
+        acc = self.attention_store.get(key, ())
+        if idx >= len(acc):
+            return None
+        t = acc[idx]
+        ok = self._acc_geometry.get((key, idx))
+        if ok is None or ok[0] is not t:
+            ok = self._acc_geometry[(key, idx)] = (t, t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape
+                                                   and t.stride() == (shape[1] * ld, ld, 1) and t.data_ptr() % 16 == 0)
+        return (idx, t) if ok[1] else None
+
+    def kernel_did(self, edit, acc_key=None):
+        """HookAdapter around the controller call of one layer: the probability kernel has applied this step's edit to the probabilities
+        (`edit`) and added them to attention_store[key][index] (`acc_key`).  `kernel_did(False)` once the call is over."""
+        self.kernel_edit = edit
+        if acc_key is not None:
+            self._fused_acc.add(acc_key)
+
     def reset(self):
         super().reset()
         self.step_store = self.get_empty_store()
         self.attention_store = {}
+        self.kernel_edit = False
         self._fused_acc = set()
-        self._epi_acc_ok = {}
+        self._acc_geometry = {}
 
 
-class AttentionControlEdit(AttentionStore, abc.ABC):
+class PromptGroupEdit(AttentionStore):
+    """The prompt-group view of an edit: the conditional rows are G independent groups of P prompts [base | edits] x heads, group-major.
+    A subclass states its `layout`, `self_window(step)` (True, False, or None when the groups disagree), `_edit_operator(step, dev)` and
+    the torch expressions `edit_rows_torch`."""
+
+    def __init__(self, layout):
+        super().__init__()
+        self.layout = layout
+        self._edit_ops = {}            # (step, device) -> cross_edit_operator
+
+    def cross_edit_operator(self, step, dev):
+        """The packed operators (ops.p2p_pack_operator) of  a_t * replace_cross_attention(base, cur) + (1 - a_t) * cur  at `step`, ordered
+        [group][edit] ([G*(P-1), 96, 80] fp16 / [G*(P-1), 96] fp32), cached on `dev`."""
+        key = (int(step), str(dev))
+        if key not in self._edit_ops:
+            self._edit_ops[key] = self._edit_operator(step, dev)
+        return self._edit_ops[key]
+
+    def forward(self, attn, is_cross: bool, place_in_unet: str):
+        super().forward(attn, is_cross, place_in_unet)          # stores a VIEW (of all groups' rows): the stored tensor sees the edit below
+        if self.layout is None or self.kernel_edit:             # nothing to edit, or the probability kernel's epilogue has done it already
+            return attn
+        return self.edit_rows(attn, is_cross, place_in_unet)
+
+    def edit_rows(self, attn, is_cross: bool, place_in_unet: str):
+        """This step's edit of the conditional rows (forward after storing the view)."""
+        G, P = self.layout
+        if is_cross and attn.is_cuda and attn.shape[0] % (G * P) == 0:
+            from . import ops                                    # fused in-place HIP kernel (matrix cores, fp32 accumulate), all groups
+            if ops.p2p_cross_edit_supported(attn):               # the executor's 80-column rows; else the torch path
+                At, Dp = self.cross_edit_operator(self.cur_step, attn.device)
+                return ops.p2p_cross_edit_groups(attn, G, P, At, Dp)
+        return self.edit_rows_torch(attn, is_cross, place_in_unet)
+
+
+class AttentionControlEdit(PromptGroupEdit, abc.ABC):
     """Cross/self attention injection between a base prompt (row group 0) and its edits (utils/p2p.py:176-221)."""
 
     def __init__(self, prompts, num_steps: int, cross_replace_steps, self_replace_steps, local_blend: Optional[LocalBlend]):
-        super().__init__()
+        super().__init__((1, len(prompts)))
         self.batch_size = len(prompts)
         self.cross_replace_alpha = get_time_words_attention_alpha(prompts, num_steps, cross_replace_steps, tokenizer).to(device)
         if type(self_replace_steps) is float:
             self_replace_steps = 0, self_replace_steps
         self.num_self_replace = int(num_steps * self_replace_steps[0]), int(num_steps * self_replace_steps[1])
         self.local_blend = local_blend
-
-    def needs_probs(self, is_cross, n_queries, place_in_unet):
-        return is_cross or n_queries <= self.STORE_MAX_QUERIES
 
     def step_callback(self, x_t):
         return x_t if self.local_blend is None else self.local_blend(x_t, self.attention_store)
@@ -294,42 +377,23 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
     def replace_cross_attention(self, attn_base, att_replace):
         raise NotImplementedError
 
-    # ---- the same edit as one linear operator per step (device path: ops.p2p_cross_edit, csrc/p2p.hip) -------------
+    # ---- the same edit as one linear operator per step (device path: ops.p2p_cross_edit_groups, csrc/p2p.hip) -------------
     def cross_edit_terms(self, dev):
         """(A0 [P-1, T, T], D0 [P-1, T]) fp32 on `dev` with  replace_cross_attention(base, cur)[b] == base . A0[b] + D0[b] * cur[b]."""
         raise NotImplementedError
 
-    def cross_edit_operator(self, step, dev):
-        """The packed operator (ops.p2p_pack_operator) of  a_t * replace_cross_attention(base, cur) + (1 - a_t) * cur  for
-        this step, cached on `dev`."""
-        key = (int(step), str(dev))
-        cache = self.__dict__.setdefault("_edit_ops", {})
-        if key not in cache:                 # built on `dev` with torch ops: no host round trip (a sync inside the UNet's
-            A0, D0 = self.cross_edit_terms(dev)                           # hook callbacks would serialise CPU and GPU)
-            a = self.cross_replace_alpha[step].reshape(self.batch_size - 1, -1).to(dev, torch.float32)       # [P-1, T]
-            from . import ops
-            cache[key] = ops.p2p_pack_operator(A0 * a[:, None, :], D0 * a + (1.0 - a))
-        return cache[key]
-
-    def forward(self, attn, is_cross: bool, place_in_unet: str):
-        super().forward(attn, is_cross, place_in_unet)          # stores a VIEW: the stored tensor sees the edit below
-        if getattr(self, "_kernel_edit", False):                # the probability kernel's epilogue has applied this layer's edit already
-            return attn
-        return self.edit_rows(attn, is_cross, place_in_unet)
+    def _edit_operator(self, step, dev):
+        A0, D0 = self.cross_edit_terms(dev)  # built on `dev` with torch ops: no host round trip (a sync inside the UNet's hook
+        a = self.cross_replace_alpha[step].reshape(self.batch_size - 1, -1).to(dev, torch.float32)   # callbacks would serialise CPU and GPU)
+        from . import ops
+        return ops.p2p_pack_operator(A0 * a[:, None, :], D0 * a + (1.0 - a))
 
     def self_window(self, step):
         return self.num_self_replace[0] <= step < self.num_self_replace[1]
 
-    def edit_rows(self, attn, is_cross: bool, place_in_unet: str):
-        """This step's edit of one prompt group's conditional rows [base | edits] x heads (forward after storing the view)."""
-        in_self_window = self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]
-        if not (is_cross or in_self_window):
+    def edit_rows_torch(self, attn, is_cross: bool, place_in_unet: str):
+        if not (is_cross or self.self_window(self.cur_step)):
             return attn
-        if is_cross and attn.is_cuda:
-            from . import ops                                    # fused in-place HIP kernel (matrix cores, fp32 accumulate)
-            if ops.p2p_cross_edit_supported(attn):               # the executor's 80-column rows; else the torch path below
-                At, Dp = self.cross_edit_operator(self.cur_step, attn.device)
-                return ops.p2p_cross_edit(attn, self.batch_size, At, Dp)
         heads = attn.shape[0] // self.batch_size
         grouped = attn.reshape(self.batch_size, heads, *attn.shape[1:])
         base, edits = grouped[0], grouped[1:]
@@ -412,7 +476,7 @@ def make_controller(prompts: List[str], is_replace_controller: bool, cross_repla
 
 
 # ------------------------------------------------------------------------------------------- batched editing
-class ControllerBatch(AttentionStore):
+class ControllerBatch(PromptGroupEdit):
     """One controller per image for a UNet batch of G independent prompt groups [g0: P samples | g1: P samples | ...] (batched
     editing: many images edited in one call instead of a stream of batch-P calls).
 
@@ -420,8 +484,7 @@ class ControllerBatch(AttentionStore):
     prompts P, or plain AttentionStores.  The batch keeps ONE store tensor per layer (all groups' rows: the probability kernel's
     store epilogue keeps working); after every step each member's attention_store holds views of its own rows and its counters
     (cur_step, cur_att_layer, LocalBlend.counter) stand where a run of its own would have left them, so get_average_attention() and
-    the LocalBlend of every image work per image.  The cross-attention edit is one launch for all groups (icd_p2p_cross_edit_groups,
-    or the probability kernel's epilogue with group_count = G), LocalBlend one launch (icd_local_blend_groups)."""
+    the LocalBlend of every image work per image."""
 
     EDIT_TYPES = ("AttentionReplace", "AttentionRefine", "AttentionReweight")
 
@@ -440,7 +503,8 @@ class ControllerBatch(AttentionStore):
             raise ValueError("ControllerBatch: members must all be make_controller edit controllers or all plain AttentionStores, "
                              f"got {sorted({type(c).__name__ for c in members})}")
         self.members = members
-        super().__init__()
+        self._blend_terms = {}         # LocalBlend.blend_groups' cache for the members' LocalBlends
+        super().__init__((len(members), self.n_prompts) if self.is_edit else None)
 
     @property
     def n_groups(self):
@@ -456,34 +520,16 @@ class ControllerBatch(AttentionStore):
         for m in self.members:
             m.num_att_layers = n
 
-    def needs_probs(self, is_cross, n_queries, place_in_unet):
-        return (self.is_edit and is_cross) or n_queries <= self.STORE_MAX_QUERIES
-
     def self_window(self, step):
-        """True / False when every member is inside / outside its self-replace window at `step`, None when they disagree."""
         w = {m.self_window(step) for m in self.members}
         return w.pop() if len(w) == 1 else None
 
-    def cross_edit_operator(self, step, dev):
-        """The members' packed operators of this step concatenated ([G*(P-1), 96, 80] / [G*(P-1), 96]), cached on `dev`."""
-        key = (int(step), str(dev))
-        cache = self.__dict__.setdefault("_edit_ops", {})
-        if key not in cache:
-            ops_ = [m.cross_edit_operator(step, dev) for m in self.members]
-            cache[key] = (torch.cat([a for a, _ in ops_]).contiguous(), torch.cat([d for _, d in ops_]).contiguous())
-        return cache[key]
+    def _edit_operator(self, step, dev):
+        ops_ = [m.cross_edit_operator(step, dev) for m in self.members]
+        return torch.cat([a for a, _ in ops_]).contiguous(), torch.cat([d for _, d in ops_]).contiguous()
 
-    def forward(self, attn, is_cross: bool, place_in_unet: str):
-        super().forward(attn, is_cross, place_in_unet)          # one stored view of all groups' rows
-        if not self.is_edit or getattr(self, "_kernel_edit", False):
-            return attn
-        G, P = self.n_groups, self.n_prompts
-        if is_cross and attn.is_cuda:
-            from . import ops
-            if ops.p2p_cross_edit_supported(attn) and attn.shape[0] % (G * P) == 0:
-                At, Dp = self.cross_edit_operator(self.cur_step, attn.device)
-                return ops.p2p_cross_edit_groups(attn, G, P, At, Dp)
-        rows = attn.shape[0] // G
+    def edit_rows_torch(self, attn, is_cross: bool, place_in_unet: str):
+        rows = attn.shape[0] // self.n_groups
         for g, m in enumerate(self.members):                     # per group: the member's own edit on its own rows
             v = attn[g * rows:(g + 1) * rows]
             new = m.edit_rows(v, is_cross, place_in_unet)
@@ -498,16 +544,11 @@ class ControllerBatch(AttentionStore):
 
     def between_steps(self):
         super().between_steps()
-        self._share()
-
-    def _share(self):
-        """Every member's store: views of its own rows of the batch's tensors."""
         G = self.n_groups
-        for g, m in enumerate(self.members):
+        for g, m in enumerate(self.members):                     # every member's store: views of its own rows of the batch's tensors
             m.attention_store = {key: [t[g * (t.shape[0] // G):(g + 1) * (t.shape[0] // G)] for t in ts]
                                  for key, ts in self.attention_store.items()}
             m.step_store = m.get_empty_store()
-            m._fused_acc = set()
 
     def reset(self):
         super().reset()
@@ -521,41 +562,15 @@ class ControllerBatch(AttentionStore):
         if x_t.shape[0] != G * P:
             raise ValueError(f"ControllerBatch.step_callback: {x_t.shape[0]} latents for {G} groups of {P} prompts")
         lbs = [m.local_blend for m in self.members]
-        active = []
-        for lb in lbs:                                           # each member's LocalBlend counter advances as in a run of its own
-            if lb is not None:
-                lb.counter += 1
-            active.append(lb is not None and lb.counter > lb.start_blend)
+        active = [lb is not None and lb.due() for lb in lbs]     # each member's LocalBlend counter advances as in a run of its own
         if not any(active):
             return x_t
         layers, side = LocalBlend.select_maps(self.attention_store, x_t)
-        if LocalBlend._on_device(x_t, layers, side) and all(lb is None or lb.alpha_layers.shape[0] == P for lb in lbs):
-            from . import ops
-            alpha, sub, th_pool, th_sub = self._blend_terms(lbs, x_t.device)
-            return ops.local_blend_groups(layers, alpha, sub, th_pool, th_sub, active, x_t.contiguous(), G, res=side[0])
-        outs = []
-        for g, (m, lb, on) in enumerate(zip(self.members, lbs, active)):
-            xg = x_t[g * P:(g + 1) * P]
-            outs.append(lb.blend(xg, m.attention_store) if on else xg)
-        return torch.cat(outs)
-
-    def _blend_terms(self, lbs, dev):
-        """(alpha [G*P, 77], (alpha_sub [G*P, 77], has_sub) or None, th_pool [G], th_sub [G]) of the members' LocalBlends, cached."""
-        key = str(dev)
-        cache = self.__dict__.setdefault("_blend_cache", {})
-        if key not in cache:
-            P = self.n_prompts
-            zero = torch.zeros(P, MAX_NUM_WORDS, device=dev)
-            alpha = torch.cat([zero if lb is None else lb.alpha_layers.reshape(P, MAX_NUM_WORDS).to(dev, torch.float32) for lb in lbs])
-            has_sub = [lb is not None and lb.substruct_layers is not None for lb in lbs]
-            sub = None
-            if any(has_sub):
-                sub = (torch.cat([lb.substruct_layers.reshape(P, MAX_NUM_WORDS).to(dev, torch.float32) if h else zero
-                                  for lb, h in zip(lbs, has_sub)]), has_sub)
-            th_pool = [0.0 if lb is None else lb.th[0] for lb in lbs]
-            th_sub = [0.0 if lb is None else lb.th[1] for lb in lbs]
-            cache[key] = (alpha, sub, th_pool, th_sub)
-        return cache[key]
+        out = LocalBlend.blend_groups(lbs, active, x_t, layers, side, self._blend_terms)
+        if out is not None:
+            return out
+        return torch.cat([m.local_blend.blend(xg, m.attention_store) if on else xg
+                          for m, on, xg in zip(self.members, active, x_t.split(P))])
 
 
 # ------------------------------------------------------------------------------------------- registration
@@ -582,6 +597,19 @@ def register_attention_control(model, controller):
         controller.num_att_layers = 0
 
 
+class LayerCall:
+    """One materialised layer call, from HookAdapter.query to probs_ready: the executor's buffer and what its kernel does to the probabilities."""
+    __slots__ = ("buf", "view", "half", "epilogue", "refs", "edit_done", "acc_key")
+
+    def __init__(self, half=False):
+        self.buf = self.view = None    # fp16 [rows, nq, ld] and its [:, :, :nk] view, which the controller gets
+        self.half = half               # the rows are the conditional half of a [uncond; cond] batch only
+        self.epilogue = None           # _lib.ProbsEpilogue for the kernel, or None: the controller does everything itself
+        self.refs = []                 # the tensors `epilogue` points into, alive as long as it is
+        self.edit_done = False         # the kernel applies this step's edit (cross-attention operator / base prompt's self rows)
+        self.acc_key = None            # (key, index): the kernel adds the probabilities to attention_store[key][index]
+
+
 class HookAdapter:
     """Bridges the executor's C callback (query / probs-ready per Attention module) to a controller object.
 
@@ -599,25 +627,26 @@ class HookAdapter:
         self.native = self._trusts_needs_probs(controller)
         # arena sizing hint for the executor (icd_unet_workspace_bytes_ex): 1 = the shipped controllers' rule, 2 = any layer
         self.probs_mode = 1 if self.native else 2
-        self.pending = None
-        # round 5: for the shipped controllers (exactly these classes) what they do to P - accumulate into the store, copy the base prompt's
-        # self-attention rows, the cross-attention edit operator - rides in the probability kernel's epilogue (icd_probs_epilogue): one pass
-        # over P instead of three.  `controller.fused_epilogue = False` keeps the separate passes (A/B; bit-identical results).
+        self.call = None                           # the LayerCall in flight, from query to probs_ready
+        # for exactly the shipped classes what they do to P - accumulate into the store, copy the base prompt's self-attention rows, the
+        # cross-attention edit operator - rides in the probability kernel's epilogue (module docstring)
         self.fuse = (self.native and type(controller) in (AttentionStore, AttentionReplace, AttentionRefine, AttentionReweight, ControllerBatch)
                      and getattr(controller, "fused_epilogue", True) and not LOW_RESOURCE and str(dev).startswith("cuda"))
-        self.epilogue = None
-        self._epi_refs = None
-        self._epi_acc_key = None
-        self._epi_edit = False
-        # round 5: a controller with the reference's __call__ touches the second half of a [uncond; cond] batch only (utils/p2p.py:153-155).
-        # The executor then writes P for those samples alone and runs the unconditional half through the fused kernel (hook return 2):
-        # half the probabilities written, read back by P.V and held by the caching allocator.  `controller.cond_rows_only = False` keeps
-        # the whole batch materialised (A/B; the conditional rows and every stored tensor are the same bits either way).
+        # a controller with the reference's __call__ touches the second half of a [uncond; cond] batch only (utils/p2p.py:153-155).  The
+        # executor then writes P for those samples alone and runs the unconditional half through the fused kernel (hook return 2): half
+        # the probabilities written, read back by P.V and held by the caching allocator
         self.half_ok = (self.native and not cond_only and not LOW_RESOURCE and isinstance(controller, AttentionControl)
                         and type(controller).__call__ is AttentionControl.__call__ and batch > 0 and batch % 2 == 0
                         and getattr(controller, "cond_rows_only", True) and str(dev).startswith("cuda"))
-        self.half = False
         self.batch = batch                         # samples of the UNet batch ([uncond; cond] when not cond_only); 0 = unknown
+
+    @property
+    def half(self):                                # of the layer call in flight, as `epilogue`
+        return self.call is not None and self.call.half
+
+    @property
+    def epilogue(self):
+        return None if self.call is None else self.call.epilogue
 
     @staticmethod
     def _trusts_needs_probs(c):
@@ -642,103 +671,75 @@ class HookAdapter:
                 c.tick()
             return None
         # a FRESH buffer per layer call: AttentionStore keeps views of it alive across steps (utils/p2p.py:148,153-157)
-        self.half = self.half_ok and bh % 2 == 0
-        rows = bh // 2 if self.half else bh
-        buf = torch.empty((rows, nq, ld), dtype=torch.float16, device=self.dev)
-        self.pending = buf[:, :, :nk]
-        self.epilogue = self._plan_epilogue(is_cross, place, rows, nq, nk, ld) if self.fuse else None
-        return buf
+        half = self.half_ok and bh % 2 == 0
+        rows = bh // 2 if half else bh
+        call = self.plan(is_cross, place, rows, nq, nk, ld, half) if self.fuse else LayerCall(half)
+        call.buf = torch.empty((rows, nq, ld), dtype=torch.float16, device=self.dev)
+        call.view = call.buf[:, :, :nk]
+        self.call = call
+        return call.buf
 
-    def _plan_epilogue(self, is_cross, place, bh, nq, nk, ld):
-        """icd_probs_epilogue of this layer call, or None: which of the controller's operations on P the kernel performs itself."""
-        from . import _lib
+    def plan(self, is_cross, place, bh, nq, nk, ld, half=False):
+        """The LayerCall of a layer whose buffer holds `bh` = samples x heads rows, without its buffer: which of the controller's operations
+        on P the probability kernel performs itself (icd_probs_epilogue).  Nothing is launched or allocated."""
+        from . import _lib, ops
         c = self.c
-        self._epi_refs, self._epi_acc_key, self._epi_edit = None, None, False
-        first = 0 if (self.cond_only or self.half) else bh // 2
+        call = LayerCall(half)
+        first = 0 if (self.cond_only or half) else bh // 2
         rows = bh - first
         epi = _lib.ProbsEpilogue()
         epi.first_cond_row = first
-        refs = []
-        if isinstance(c, ControllerBatch) and c.is_edit:
-            # G prompt groups of P on the conditional samples: operators [group][edit], each group's self rows from its own base
-            # (group_count = G); a self layer whose members disagree about their self-replace windows takes the separate passes
-            G, P = c.n_groups, c.n_prompts
+        if c.layout is not None:
+            # operators [group][edit], each group's self rows from its own base.  The kernel indexes them by SAMPLE (prompt jp of its group,
+            # operator jp - 1), while the controller - like the reference (utils/p2p.py:192-194) - groups the rows by heads = rows / P: the
+            # two agree only when the conditional samples of this call are exactly the controller's prompts.  Anything else (more latents
+            # than prompts, an unknown batch) keeps the separate passes.
+            G, P = c.layout
             cond = (self.batch if self.cond_only else self.batch // 2) if self.batch > 0 else 0
             if rows % (G * P) != 0 or P < 2 or cond != G * P:
-                return None
+                return call
             epi.edit_count, epi.group_count = P - 1, G
             if is_cross:
-                if not (nk <= 80 and ld >= 80 and ld % 8 == 0):
-                    return None
+                if not ops.p2p_cross_edit_geometry(nk, ld):
+                    return call                      # the torch / icd_p2p_cross_edit_groups path handles it (and then the store add must follow it)
                 At, Dp = c.cross_edit_operator(c.cur_step, self.dev)
                 epi.edit_At, epi.edit_D = At.data_ptr(), Dp.data_ptr()
-                refs += [At, Dp]
-                self._epi_edit = True
-            else:
+                call.refs += [At, Dp]
+                call.edit_done = True
+            else:                                    # (materialised self-attention layers are the <= 32^2-query ones: always replaced)
                 win = c.self_window(c.cur_step)
-                if win is None:
-                    return None
+                if win is None:                      # the groups disagree about their self-replace windows: the separate passes
+                    return call
                 if win:
                     epi.self_from_base = 1
-                    self._epi_edit = True
-        elif isinstance(c, AttentionControlEdit):
-            # the kernel indexes the edit operators by SAMPLE (prompt jp = sample - first conditional sample, jp - 1 operators), while the
-            # controller - like the reference (utils/p2p.py:192-194) - groups the rows by heads = rows / batch_size: the two agree only when
-            # the conditional samples of this call are exactly the controller's prompts.  Anything else (more latents than prompts, an
-            # unknown batch) keeps the separate passes.
-            cond = (self.batch if self.cond_only else self.batch // 2) if self.batch > 0 else 0
-            if rows % c.batch_size != 0 or c.batch_size < 2 or cond != c.batch_size:
-                return None
-            epi.edit_count = c.batch_size - 1
-            if is_cross:
-                if not (nk <= 80 and ld >= 80 and ld % 8 == 0):
-                    return None                      # the torch / icd_p2p_cross_edit path handles it (and then the store add must follow it)
-                At, Dp = c.cross_edit_operator(c.cur_step, self.dev)
-                epi.edit_At, epi.edit_D = At.data_ptr(), Dp.data_ptr()
-                refs += [At, Dp]
-                self._epi_edit = True
-            elif c.num_self_replace[0] <= c.cur_step < c.num_self_replace[1]:
-                epi.self_from_base = 1               # (materialised self-attention layers are the <= 32^2-query ones: always replaced)
-                self._epi_edit = True
-        if nq <= c.STORE_MAX_QUERIES and c.attention_store:
+                    call.edit_done = True
+        if nq <= c.STORE_MAX_QUERIES:
             key = f"{place}_{'cross' if is_cross else 'self'}"
-            idx = len(c.step_store[key])
-            acc = c.attention_store.get(key, [])
-            if idx < len(acc):
-                t = acc[idx]
-                seen = c.__dict__.setdefault("_epi_acc_ok", {})      # geometry checked once per stored tensor, not once per step
-                ok = seen.get((key, idx))
-                if ok is None or ok[0] is not t:
-                    ok = (t, t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == (rows, nq, nk) and t.stride() == (nq * ld, ld, 1)
-                          and t.data_ptr() % 16 == 0, t.data_ptr() if t.is_cuda else 0)
-                    seen[(key, idx)] = ok
-                if ok[1]:
-                    epi.acc = ok[2]
-                    refs.append(t)
-                    self._epi_acc_key = (key, idx)
-        if not (self._epi_edit or self._epi_acc_key):
-            return None
-        self._epi_refs = refs
-        return epi
+            target = c.store_target(key, (rows, nq, nk), ld)
+            if target is not None:
+                epi.acc = target[1].data_ptr()
+                call.refs.append(target[1])
+                call.acc_key = (key, target[0])
+        if call.edit_done or call.acc_key:
+            call.epilogue = epi
+        return call
 
     def probs_ready(self, layer, is_cross, place):
-        view, self.pending = self.pending, None
+        call, self.call = self.call, None
         c = self.c
-        fused, self.epilogue = self.epilogue is not None, None
+        fused = call.epilogue is not None
         if fused:                                    # tell the controller what the kernel has done to this layer's P
-            c._kernel_edit = self._epi_edit
-            if self._epi_acc_key is not None:
-                c._fused_acc.add(self._epi_acc_key)
+            c.kernel_did(call.edit_done, call.acc_key)
         try:
-            if (self.cond_only or self.half) and isinstance(c, AttentionControl):
-                c.call_cond_only(view, is_cross, place)
+            if (self.cond_only or call.half) and isinstance(c, AttentionControl):
+                c.call_cond_only(call.view, is_cross, place)
                 return
-            out = c(view, is_cross, place)
-            if out is not None and out is not view:
-                view.copy_(out)
+            out = c(call.view, is_cross, place)
+            if out is not None and out is not call.view:
+                call.view.copy_(out)
         finally:
             if fused:
-                c._kernel_edit = False
+                c.kernel_did(False)
 
 
 # ------------------------------------------------------------------------------------------- word / schedule helpers

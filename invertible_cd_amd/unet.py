@@ -458,9 +458,10 @@ class UNet2DConditionModel:
                         return 0
                     live.append(buf)
                     probs_pp[0] = buf.data_ptr()
-                    if adapter.epilogue is not None:         # the controller's work on P rides in the kernel's epilogue
-                        probs_pp[1] = C.addressof(adapter.epilogue)
-                    return 2 if adapter.half else 1          # 2: `buf` holds the second half of the batch only (the conditional rows)
+                    call = adapter.call                      # p2p.LayerCall: what query planned for this layer call
+                    if call.epilogue is not None:            # the controller's work on P rides in the kernel's epilogue
+                        probs_pp[1] = C.addressof(call.epilogue)
+                    return 2 if call.half else 1             # 2: `buf` holds the second half of the batch only (the conditional rows)
                 adapter.probs_ready(layer, bool(is_cross), PLACES[place])
                 return 0
             except BaseException as e:       # never let an exception cross the C boundary

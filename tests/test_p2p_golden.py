@@ -191,11 +191,11 @@ def test_fused_epilogue_is_planned_only_when_the_samples_are_the_controllers_pro
     for batch, cond_only, want in [(2, True, True), (4, True, False), (4, False, True), (8, False, False), (0, True, False), (3, True, False)]:
         ad = p2p.HookAdapter(c, cond_only=cond_only, dev="cpu", batch=batch)
         bh = max(batch, 2) * heads
-        epi = ad._plan_epilogue(True, "down", bh, 256, 77, 80)
+        epi = ad.plan(True, "down", bh, 256, 77, 80).epilogue
         assert (epi is not None and bool(epi.edit_At)) == want, (batch, cond_only)
         if want:
             assert epi.edit_count == 1 and epi.first_cond_row == (0 if cond_only else bh // 2)
-        epi = ad._plan_epilogue(False, "down", bh, 256, 256, 256)                       # self-attention replacement (step 0 is inside its window)
+        epi = ad.plan(False, "down", bh, 256, 256, 256).epilogue                        # self-attention replacement (step 0 is inside its window)
         assert (epi is not None and epi.self_from_base == 1) == want, (batch, cond_only)
 
 
