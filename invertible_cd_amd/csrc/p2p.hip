@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_kernel(half_t* __restrict_
 //   * in the blend kernel itself (no workspace): block p rebuilds the base prompt's heat next to its own - a few hundred KB at SD1.5's
 //     five 16 x 16 layers.
 // The blend kernel, block p = prompt p:
-//   on_q = (maxpool3x3(heat_q) / max(maxpool3x3(heat_q))) > th_pool                                      (pad = -inf, stride 1)
+//   on_q = (maxpool3x3(heat_q) / max(maxpool3x3(heat_q))) > th_pool        (pad = -inf, stride 1; max over the pixels the resize reads)
 //   mask_p = on_0 | on_p ;  with substruct words: mask_p &= ~(sub_0 | sub_p), sub_q = (heat'_q / max heat'_q) > th_sub, no pooling
 //   out[p] = x[0] + float(mask_p, nearest-resized to H x W) * (x[p] - x[0])     (difference in x's dtype, the rest fp32: torch's
 //                                                                               promotion of `base + mask.float() * (x_t - base)`)
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void local_blend_heat_kernel(HeatArgs a) {
 
 __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
     __shared__ float heat[1024], pooled[1024], red[4];
-    __shared__ unsigned char mask[1024], on_tmp[1024];
+    __shared__ unsigned char mask[1024], on_tmp[1024], hit_y[32], hit_x[32];
     const int p = blockIdx.x, gl = blockIdx.y, tid = threadIdx.x, res2 = a.res * a.res;
     const long long per = (long long)a.C * a.H * a.W;
     const long long q0 = (long long)gl * a.P;                 // the group's base prompt
@@ -167,6 +167,13 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
     int total_heads = 0;
     for (int l = 0; l < a.n_layers; ++l) total_heads += a.heads[l];
     for (int i = tid; i < res2; i += 256) mask[i] = 0;
+    // The reference normalises AFTER its nearest resize: the maximum is over the map pixels the resize reads - all of them when
+    // H, W >= res, every other one of a 16 x 16 map under an 8 x 8 latent.
+    const float sy = (float)a.res / (float)a.H, sx = (float)a.res / (float)a.W;
+    if (tid < 32) hit_y[tid] = hit_x[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < a.H; i += 256) hit_y[min((int)floorf(i * sy), a.res - 1)] = 1;
+    for (int i = tid; i < a.W; i += 256) hit_x[min((int)floorf(i * sx), a.res - 1)] = 1;
     __syncthreads();
     // pass 0 / 1: main words of prompt 0 / p (pooled, OR-ed into mask); pass 2 / 3: substruct words (cleared from mask)
     const int npass = (a.alpha_sub && (a.flags[gl] & 2)) ? 4 : 2;
@@ -192,8 +199,8 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
         float mx = -INFINITY;
         for (int pix = tid; pix < res2; pix += 256) {
             float v = heat[pix];
+            const int y = pix / a.res, x = pix - y * a.res;
             if (!sub) {                                             // 3x3 max pool, stride 1, padding 1 (out-of-range taps ignored)
-                const int y = pix / a.res, x = pix - y * a.res;
                 for (int dy = -1; dy <= 1; ++dy)
                     for (int dx = -1; dx <= 1; ++dx) {
                         const int yy = y + dy, xx = x + dx;
@@ -201,7 +208,7 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
                     }
             }
             pooled[pix] = v;
-            mx = fmaxf(mx, v);
+            if (hit_y[y] && hit_x[x]) mx = fmaxf(mx, v);
         }
         mx = wave_max(mx);                                          // (a maximum does not depend on the order it is taken in)
         if ((tid & 63) == 0) red[tid >> 6] = mx;
@@ -221,7 +228,6 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendArgs a) {
         __syncthreads();
     }
     // blend
-    const float sy = (float)a.res / (float)a.H, sx = (float)a.res / (float)a.W;
     for (long long i = tid; i < per; i += 256) {
         const int xw = (int)(i % a.W), yh = (int)((i / a.W) % a.H);
         const int my = min((int)floorf(yh * sy), a.res - 1), mxi = min((int)floorf(xw * sx), a.res - 1);

@@ -607,10 +607,14 @@ def accumulate_multi(dst, src):
     """dst[t] += src[t] for lists of fp16 cuda tensors in one launch, rounded like torch's in-place add.  Up to 32 tensors travel in the
     kernel's arguments (icd_accumulate_multi); more - an SDXL step stores 130 maps - in a table on the device (icd_accumulate_multi_n)."""
     lib = _lib.load()
-    n = len(dst)
-    assert n == len(src) and n > 0
+    assert len(dst) == len(src) and len(dst) > 0
     for a, b in zip(dst, src):
         assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float16 and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+    # an empty tensor has no address (data_ptr() is 0) and the <= 32-tensor entry refuses a null pointer: nothing to add, left out
+    dst, src = [a for a in dst if a.numel()], [b for b in src if b.numel()]
+    n = len(dst)
+    if n == 0:
+        return
     if n <= 32:
         dp, sp, cn = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
         for t, (a, b) in enumerate(zip(dst, src)):

@@ -7,24 +7,27 @@ N_WORDS = 77
 MAIN_WORDS, SUB_WORDS = (2, 5), (7,)
 
 
-def blend_inputs(seed, P, heads, n_layers, res, latent, x_dtype=torch.float16):
-    """(maps: n_layers fp16 CPU tensors [P * heads, res * res, 77], alpha [P, 77], alpha_sub [P, 77], x [P, 4, latent, latent])."""
+def blend_inputs(seed, P, heads, n_layers, res, latent, x_dtype=torch.float16, layer_heads=None, channels=4, n_words=N_WORDS):
+    """(maps: n_layers fp16 CPU tensors [P * heads, res * res, 77], alpha [P, 77], alpha_sub [P, 77], x [P, 4, latent, latent]).
+    layer_heads: a list of head counts, one per layer (then `heads` and `n_layers` are not read); latent: a side or (H, W); channels and
+    n_words: of x and of the maps.  The defaults draw what they always drew."""
     gen = torch.Generator().manual_seed(seed)
     yy, xx = torch.meshgrid(torch.arange(res).float(), torch.arange(res).float(), indexing="ij")
     s = res / 16.0
     centres = {2: (4.0, 5.0), 5: (11.0, 9.0), 7: (8.0, 3.0)}
     maps = []
-    for li in range(n_layers):
-        m = torch.rand(P * heads, res * res, N_WORDS, generator=gen) * 0.02
+    for li, h in enumerate([heads] * n_layers if layer_heads is None else layer_heads):
+        m = torch.rand(P * h, res * res, n_words, generator=gen) * 0.02
         for w, (cy, cx) in centres.items():
             blob = torch.exp(-((yy - s * cy - 0.05 * s * li) ** 2 + (xx - s * cx) ** 2) / (8.0 * s * s)).reshape(1, res * res)
-            m[:, :, w] = m[:, :, w] * 10.0 * (0.05 + blob) * (1 + 0.1 * torch.rand(P * heads, 1, generator=gen))
+            m[:, :, w] = m[:, :, w] * 10.0 * (0.05 + blob) * (1 + 0.1 * torch.rand(P * h, 1, generator=gen))
         maps.append(m.half())
-    alpha = torch.zeros(P, N_WORDS)
+    alpha = torch.zeros(P, n_words)
     alpha[:, list(MAIN_WORDS)] = 1
-    sub = torch.zeros(P, N_WORDS)
+    sub = torch.zeros(P, n_words)
     sub[:, list(SUB_WORDS)] = 1
-    x = torch.randn(P, 4, latent, latent, generator=gen).to(x_dtype)
+    H, W = (latent, latent) if isinstance(latent, int) else latent
+    x = torch.randn(P, channels, H, W, generator=gen).to(x_dtype)
     return maps, alpha, sub, x
 
 
