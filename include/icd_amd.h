@@ -281,6 +281,16 @@ int icd_attention_masked(const void* q, const void* k, const void* vt, void* out
                          int32_t Nq, int32_t Nk, int32_t d, int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo,
                          int64_t vt_batch_stride, float scale, void* stream);
 
+/* Flash attention at head dims above icd_attention_fused's 160 (the mid-block attention of AutoencoderKL: ONE head as wide as the
+ * block, 512 channels at the SD / SDXL width, vae/decode and vae/encode of utils/generation.py and utils/generation_sdxl.py): no
+ * [B, Nq, Nk] score or probability buffer, whatever the image size.  Layouts and arguments of icd_attention_fused; d a multiple of 8
+ * in 168 ... 512 (anything else returns ICD_ERR_UNSUPPORTED before a launch), any B, H, Nq >= 1, Nk >= 1; not causal, no prescaled
+ * form.  The head dim is split over the 2 - 4 waves of a block (128 columns each), which exchange partial scores through LDS and sum
+ * them in a fixed order: the result is deterministic.  The pad columns [Nk, ldvt) of vt may hold anything (the kernel masks the V^T
+ * fragment as well as the scores). */
+int icd_attention_wide(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t d,
+                       int32_t ldq, int32_t ldk, int32_t ldvt, int32_t ldo, int64_t vt_batch_stride, float scale, void* stream);
+
 /* LayerNorm over the last dim of an fp32 [rows, C] stream (affine, exact two-pass variance about a mean summed in double): the
  * post-LayerNorm block x <- LN(x + f(x)) with the sum taken from icd_gemm_desc.out_f32, no fp16 rounding between the sum and its
  * LayerNorm.  out16 (fp16, for the next GEMM) and out32 (fp32, for the next residual add): either may be NULL, not both.
@@ -331,13 +341,15 @@ int icd_attention_probs_ex(const void* q, const void* q_carry, const void* k, co
 
 /* What an attention entry would run for a shape (pure host function: nothing is enqueued, no HIP call, works without a GPU).  The
  * query holds the arguments the dispatch reads: entry 0 = icd_attention_fused_ex (flags: ICD_ATTN_*), 1 = icd_attention_probs* (ldp;
- * split: carries present; epi: 0 no epilogue, 1 acc / self_from_base, 2 the cross edit), 2 = icd_attention_masked.  It is the entry's
+ * split: carries present; epi: 0 no epilogue, 1 acc / self_from_base, 2 the cross edit), 2 = icd_attention_masked,
+ * 3 = icd_attention_wide.  It is the entry's
  * own validation with every argument the query does not hold at a value that passes, then the entry's own planner: it refuses, with
  * the entry's status and message, exactly what the entry refuses on these arguments alone.
  * The answer: family 0 = attn_fused_kernel (tiled), 1 = attn_cross_kernel (K / V^T in registers), 2 = attn_probs_kernel,
- * 3 = attn_masked_kernel; variant = the row of that family's instantiation table, variants = rows in it; the row's template parameters
+ * 3 = attn_masked_kernel, 4 = attn_wide_kernel; variant = the row of that family's instantiation table, variants = rows in it; the row's template parameters
  * (KS, DT, QT, OCC, NST, MODE, DR, causal: tiled; KS, DT, STL and the run-time tiles_per_wave: cross; KS, SPLIT, EPI, FEW: probs;
- * NT, DT: masked; a field the family does not have is 0); the grid and the dynamic LDS bytes of the launch. */
+ * NT, DT: masked; NW, the waves of a block, and the per-wave KS, DT, NT: wide; a field the family does not have is 0); the grid and
+ * the LDS bytes of the launch beyond a kernel's fixed patches (dynamic: tiled; the two exchange buffers: wide). */
 typedef struct {
     int32_t entry;
     int32_t B, H, Nq, Nk, d;
@@ -352,6 +364,7 @@ typedef struct {
     int32_t SPLIT, EPI, FEW;
     int32_t NT;
     int32_t grid_x, grid_y, grid_z, lds_bytes;
+    int32_t NW;
 } icd_attention_info;
 int icd_attention_plan(const icd_attention_query* q, icd_attention_info* out);
 

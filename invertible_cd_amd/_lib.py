@@ -77,14 +77,14 @@ class ProbsEpilogue(C.Structure):
 
 
 class AttentionQuery(C.Structure):
-    """icd_attention_query: entry 0 fused (flags), 1 probs (ldp, split, epi 0 / 1 / 2), 2 masked."""
+    """icd_attention_query: entry 0 fused (flags), 1 probs (ldp, split, epi 0 / 1 / 2), 2 masked, 3 wide."""
     _fields_ = [(n, C.c_int32) for n in ("entry", "B", "H", "Nq", "Nk", "d", "ldp", "flags", "split", "epi")]
 
 
 class AttentionInfo(C.Structure):
-    """icd_attention_info: family 0 tiled, 1 cross, 2 probs, 3 masked; variant = the row of that family's instantiation table."""
+    """icd_attention_info: family 0 tiled, 1 cross, 2 probs, 3 masked, 4 wide; variant = the row of that family's instantiation table."""
     _fields_ = [(n, C.c_int32) for n in ("family", "variant", "variants", "KS", "DT", "QT", "OCC", "NST", "MODE", "DR", "causal", "STL",
-                                         "tiles_per_wave", "SPLIT", "EPI", "FEW", "NT", "grid_x", "grid_y", "grid_z", "lds_bytes")]
+                                         "tiles_per_wave", "SPLIT", "EPI", "FEW", "NT", "grid_x", "grid_y", "grid_z", "lds_bytes", "NW")]
 
 
 class GemmPlanInfo(C.Structure):
@@ -182,6 +182,7 @@ SIGNATURES = {
     "icd_attention_fused_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 9
                                + [C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
     "icd_attention_masked": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 9 + [C.c_int64, C.c_float, C.c_void_p]),
+    "icd_attention_wide": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 9 + [C.c_int64, C.c_float, C.c_void_p]),
     "icd_layernorm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "icd_activation": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),

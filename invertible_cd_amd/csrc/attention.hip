@@ -1272,12 +1272,13 @@ extern "C" int icd_attention_fused_ex(const void* q, const void* k, const void* 
 // widest aligned leading dims, the default V^T stride, an epilogue of the asked kind with nothing else set.
 extern "C" int icd_attention_plan(const icd_attention_query* q, icd_attention_info* out) {
     ICD_CHECK_ARG(q && out, "icd_attention_plan: null argument");
-    ICD_CHECK_ARG(q->entry >= 0 && q->entry <= 2, "icd_attention_plan: entry must be 0 (fused), 1 (probs) or 2 (masked), got %d", q->entry);
+    ICD_CHECK_ARG(q->entry >= 0 && q->entry <= 3, "icd_attention_plan: entry must be 0 (fused), 1 (probs), 2 (masked) or 3 (wide), got %d", q->entry);
     *out = icd_attention_info{};
     void* const ptr = (void*)16;
     constexpr int32_t LD = INT32_MAX - 7;
     const AttnArgs a{ptr, ptr, ptr, ptr, q->B, q->H, q->Nq, q->Nk, q->d, LD, LD, LD, LD, 0, 1.0f};
     if (q->entry == 2) return attn_masked_decide(a, (const int32_t*)ptr, out);
+    if (q->entry == 3) return attn_wide_decide(a, out);
     if (q->entry == 0) {
         const int rc = fused_validate(a, q->flags);
         if (rc == ICD_OK) fused_plan(q->B, q->H, q->Nq, q->Nk, q->d, q->flags, out);

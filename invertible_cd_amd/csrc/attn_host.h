@@ -1,4 +1,4 @@
-// attn_host.h - host side of the attention entries (attention.hip, attention_masked.hip): every entry is validate -> plan -> launch.
+// attn_host.h - host side of the attention entries (attention.hip, attention_masked.hip, attention_wide.hip): every entry is validate -> plan -> launch.
 // *_validate holds every refusal; *_plan is a pure function of shape and flags that names one row of its kernel family's table of
 // instantiations; *_launch turns the row into the instantiation.  The plan is the struct icd_attention_plan reports.  No device code.
 #pragma once
@@ -6,9 +6,9 @@
 #include "common.h"
 
 typedef icd_attention_info AttnPlan;
-enum AttnFamily { ATTN_TILED = 0, ATTN_CROSS = 1, ATTN_PROBS = 2, ATTN_MASKED = 3 };
+enum AttnFamily { ATTN_TILED = 0, ATTN_CROSS = 1, ATTN_PROBS = 2, ATTN_MASKED = 3, ATTN_WIDE = 4 };
 
-struct AttnArgs {             // what icd_attention_fused_ex and icd_attention_masked both take
+struct AttnArgs {             // what icd_attention_fused_ex, icd_attention_masked and icd_attention_wide all take
     const void *q, *k, *vt;
     void* out;
     int32_t B, H, Nq, Nk, d, ldq, ldk, ldvt, ldo;
@@ -16,7 +16,7 @@ struct AttnArgs {             // what icd_attention_fused_ex and icd_attention_m
     float scale;
 };
 
-// the refusals the two entries share, under the entry's name
+// the refusals those entries share, under the entry's name
 inline int attn_check_common(const char* name, const AttnArgs& a) {
     ICD_CHECK_ARG(a.q && a.k && a.vt && a.out, "%s: null pointer", name);
     ICD_CHECK_ARG(a.B > 0 && a.H > 0 && a.Nq > 0 && a.Nk > 0, "%s: empty shape", name);
@@ -34,6 +34,8 @@ inline int attn_check_common(const char* name, const AttnArgs& a) {
 
 // icd_attention_masked's validate + plan (attention_masked.hip), also behind icd_attention_plan
 int attn_masked_decide(const AttnArgs& a, const int32_t* key_counts, AttnPlan* p);
+// icd_attention_wide's validate + plan (attention_wide.hip), also behind icd_attention_plan
+int attn_wide_decide(const AttnArgs& a, AttnPlan* p);
 
 // launch(std::integral_constant<int, row>) for the row of a table of N: one compile-time expansion over the table
 template <typename F, size_t... I>

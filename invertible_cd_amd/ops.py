@@ -359,6 +359,18 @@ def attention_masked(q, k, vt, key_counts, B, H, Nq, Nk, d, scale):
     return out
 
 
+def attention_wide(q, k, vt, B, H, Nq, Nk, d, scale):
+    """attention_fused at head dims 168 ... 512 (icd_attention_wide; the one wide head of the VAE mid-block): flash style, nothing of
+    size Nq x Nk is allocated.  Not causal; the pad columns of vt may hold anything."""
+    _chk_rows(q, "q"); _chk_rows(k, "k"); _chk16(vt, "vt")
+    assert q.shape[0] == B * Nq and k.shape[0] == B * Nk and vt.dim() == 3 and vt.shape[0] == B and vt.shape[1] == H * d \
+        and q.shape[1] == H * d and k.shape[1] == H * d, "attention_wide: q [B * Nq, H * d], k [B * Nk, H * d], vt [B, H * d, ld]"
+    out = torch.empty((q.shape[0], q.shape[1]), device=q.device, dtype=torch.float16)
+    _lib.check(_lib.load().icd_attention_wide(_p(q), _p(k), _p(vt), _p(out), B, H, Nq, Nk, d, q.stride(0), k.stride(0), vt.stride(1),
+                                              out.stride(0), vt.stride(0), scale, _stream()), "icd_attention_wide")
+    return out
+
+
 def layernorm_f32(x32, gamma, beta, eps, want16=True, want32=True):
     """LayerNorm of the fp32 rows x32 [rows, C] (icd_layernorm_f32) -> (fp16 copy or None, fp32 copy or None)."""
     assert x32.is_cuda and x32.dtype == torch.float32 and x32.dim() == 2 and x32.is_contiguous(), "layernorm_f32: need contiguous cuda fp32 rows"

@@ -9,8 +9,8 @@ Drop-in for the attributes the reference touches on `model.vae` / `pipe.vae`:
 Architecture: diffusers 0.25.1 AutoencoderKL (oracle/vae_ref.py restates it and is what the GPU tests compare against).
 Everything runs on the same operators as the UNet: GroupNorm(+SiLU) `icd_groupnorm`, 3x3 / 1x1 convs as implicit GEMM
 `icd_gemm` (nearest-2x upsample folded into the loader; the encoder's bottom/right-only padding is ICD_GEMM_PAD_HI), the
-mid-block attention (one head of 512 channels) as QK^T -> row softmax -> PV (`icd_gemm` batched + `icd_softmax_rows`; the
-fused flash kernel when the head dim is <= 160), first / last convs through `icd_pack_nchw` + implicit GEMM and
+mid-block attention (one head of 512 channels) flash style (`icd_attention_wide` at head dims 168 - 512, `icd_attention_fused` up to
+160) or as QK^T -> row softmax -> PV (`icd_gemm` batched + `icd_softmax_rows`): AutoencoderKL._attention_kind, first / last convs through `icd_pack_nchw` + implicit GEMM and
 `icd_conv_out_n`.  Host-side algebra done once at load, all exact in real arithmetic:
   * post_quant_conv (1x1 + bias) is folded into decoder.conv_in; its bias rides on a ones-channel of the packed latent
     so the 3x3 conv's zero padding still sees zeros outside the image;
@@ -239,7 +239,7 @@ class AutoencoderKL:
         self._sd_ref = {k: state_dict[k] for k in cfg.state_dict_shapes()}     # masters of the fp32-fidelity weights (converted lazily)
         self._ws = None                        # split3 weights of the fp32-fidelity path, packed on first use
         self.max_chunk = max_chunk            # samples per pass (bounds the 512x512x128-channel activations and the scores)
-        self.fused_attention = fused_attention    # None: fused flash kernel when the head dim allows it (<= 160)
+        self.fused_attention = fused_attention    # None: _attention_kind's default; True: flash wherever a kernel has the head dim (<= 512); False: materialised scores
         self.carry = True                         # fp16 path: error-carried residual stream + GroupNorm over fp16 + carry (round 6); False: plain fp16 stream
         self.upsample_phases = True               # fp16 decoder: Upsample2D as four 2 x 2 convs on the input grid (4/9 of its flops); False: 3 x 3 form
 
@@ -249,6 +249,38 @@ class AutoencoderKL:
             if isinstance(a, torch.dtype):
                 self.dtype = a                 # float32 selects the fp32-fidelity arithmetic (module docstring), not just the I/O dtype
         return self
+
+    # ------------------------------------------------------------------ the mid-block attention of both paths (one head of C channels)
+    def _attention_kind(self, B, N, C, ld):
+        """"fused" (icd_attention_fused, C <= 160), "wide" (icd_attention_wide, 160 < C <= 512) or "scores" (three launches around a
+        materialised [B, N, ld] fp32 score tensor, chunked over the batch to <= 1 GiB of it)."""
+        flash = "fused" if C <= 160 else "wide" if C <= 512 else "scores"
+        if self.fused_attention is not None:
+            return flash if self.fused_attention else "scores"
+        if flash != "wide":
+            return flash
+        # The default at 160 < C <= 512: the wide kernel only where ONE sample's scores exceed the 1 GiB step of the materialised path
+        # (more than 16384 tokens: images above 1024^2, which that path cannot hold to its step at all).  Below that the wide kernel
+        # was measured slower at every size (profiles/attn_wide.txt, attention alone at d = 512, wide / materialised ms):
+        #     B = 8 N = 1024   0.076 / 0.050      B = 8 N = 4096   1.085 / 0.608      B = 2 N = 16384   4.224 / 3.552
+        # and decode with it 2 - 3 % slower per image (512^2 B = 8: 3.44 / 3.37 ms, 1024^2 B = 2: 16.18 / 15.74 ms), so the default
+        # keeps the materialised path there; fused_attention=True selects the wide kernel at any size (no N^2 memory).
+        return "wide" if N * ld * 4 > 1 << 30 else "scores"
+
+    def _attend(self, q, k, vt, B, N, C, ld, scale):
+        kind = self._attention_kind(B, N, C, ld)
+        if kind == "fused":
+            return ops.attention_fused(q, k, vt, B, 1, N, N, C, scale)
+        if kind == "wide":
+            return ops.attention_wide(q, k, vt, B, 1, N, N, C, scale)
+        o = torch.empty((B * N, C), device=q.device, dtype=torch.float16)
+        step = max(1, min(B, (1 << 30) // (N * ld * 4)))                        # <= 1 GiB of fp32 scores at a time
+        for b0 in range(0, B, step):
+            bc = min(step, B - b0)
+            s = ops.attention_scores(q[b0 * N:(b0 + bc) * N], k[b0 * N:(b0 + bc) * N], bc, 1, N, N, C, scale, ld)
+            pr = ops.softmax_rows(s.reshape(bc * N, ld), N, ld).reshape(bc, N, ld)
+            ops.attention_apply(pr, vt[b0:b0 + bc], bc, 1, N, C, out=o[b0 * N:(b0 + bc) * N])
+        return o
 
     # ------------------------------------------------------------------ fp32-fidelity path (dtype == torch.float32)
     def _split_weights(self):
@@ -338,17 +370,7 @@ class AutoencoderKL:
         ld = (N + 7) // 8 * 8
         vt = ops.project_vt(h, ws[p + "to_v.weight"], B, N, ld)
         scale = C ** -0.5
-        fused = self.fused_attention if self.fused_attention is not None else C <= 160
-        if fused:
-            o = ops.attention_fused(q, k, vt, B, 1, N, N, C, scale)
-        else:
-            o = torch.empty((B * N, C), device=x.device, dtype=torch.float16)
-            step = max(1, min(B, (1 << 30) // (N * ld * 4)))
-            for b0 in range(0, B, step):
-                bc = min(step, B - b0)
-                s_ = ops.attention_scores(q[b0 * N:(b0 + bc) * N], k[b0 * N:(b0 + bc) * N], bc, 1, N, N, C, scale, ld)
-                pr = ops.softmax_rows(s_.reshape(bc * N, ld), N, ld).reshape(bc, N, ld)
-                ops.attention_apply(pr, vt[b0:b0 + bc], bc, 1, N, C, out=o[b0 * N:(b0 + bc) * N])
+        o = self._attend(q, k, vt, B, N, C, ld, scale)
         return ops.gemm(o, w[p + "to_out.weight"], w[p + "to_out.bias"], resid=x, out_f32=True)
 
     def _mid32(self, p, x, B, H, W):
@@ -435,17 +457,7 @@ class AutoencoderKL:
         ld = (N + 7) // 8 * 8
         vt = ops.project_vt(h, w[p + "to_v.weight"], B, N, ld)
         scale = C ** -0.5
-        fused = self.fused_attention if self.fused_attention is not None else C <= 160
-        if fused:
-            o = ops.attention_fused(q, k, vt, B, 1, N, N, C, scale)
-        else:
-            o = torch.empty((B * N, C), device=x.device, dtype=torch.float16)
-            step = max(1, min(B, (1 << 30) // (N * ld * 4)))                    # <= 1 GiB of fp32 scores at a time
-            for b0 in range(0, B, step):
-                bc = min(step, B - b0)
-                s = ops.attention_scores(q[b0 * N:(b0 + bc) * N], k[b0 * N:(b0 + bc) * N], bc, 1, N, N, C, scale, ld)
-                pr = ops.softmax_rows(s.reshape(bc * N, ld), N, ld).reshape(bc, N, ld)
-                ops.attention_apply(pr, vt[b0:b0 + bc], bc, 1, N, C, out=o[b0 * N:(b0 + bc) * N])
+        o = self._attend(q, k, vt, B, N, C, ld, scale)
         oc = self._oc(x.shape[0], x.shape[1], x)
         return ops.gemm(o, w[p + "to_out.weight"], w[p + "to_out.bias"], resid=x, resid_carry=xc, out_carry=oc), oc
 
