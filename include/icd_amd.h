@@ -748,6 +748,28 @@ int icd_vae_ingest(const void* images, int32_t B, int32_t H, int32_t W, int32_t 
  * each evaluated in fp32 and rounded to x's dtype before the next step, then truncation towards zero.  +-inf clamp to 255 / 0; NaN is
  * outside the contract.  Any H, W; x aligned to its element, out 4-byte aligned.  One launch. */
 int icd_image_to_u8(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream);
+/* Real images into the fp32-fidelity VAE encoder (the SDXL route: diffusers' img2img prepare_latents upcasts the VAE), on uint8 NHWC
+ * images [B, H, W, 3] (device; `images` may start at any byte): Pillow's BICUBIC resize to S x S exactly as icd_vae_ingest makes it (the
+ * same tables, the same horizontal pass, the same vertical pass with another store), then diffusers' VaeImageProcessor.preprocess in
+ * fp32 - `np.asarray(im, float32) / 255.0`, `2.0 * x - 1.0` - and the split of icd_split_cast at scale 1, in one pass:
+ *   out   [(b * S + y) * S + x] = 24 fp16 columns, the split3 layout [hi | lo | hi] of the 8-channel packing that the split-operand
+ *         conv_in reads: for channel c < 3, v = 2.0f * (fp32(u) / 255.0f) - 1.0f (a true division, uncontracted), hi = fp16(v) in columns
+ *         c and 16 + c, lo = fp16(v - fp32(hi)) in column 8 + c; the other 15 columns are zero.  These are the bits icd_split_cast gives
+ *         for the zero-padded NHWC tensor of preprocess's output;
+ *   bytes [B, S, S, 3] uint8, the resized image itself; NULL skips it and nothing is written there.
+ * tmp: uint8 [B * H * S * 3] scratch on the device, 4-byte aligned; out 16-byte aligned; bytes at any address.  Limits as for
+ * icd_vae_ingest: S % 8 == 0, S <= 4096, W <= 4096, tables of another row length are refused.  64-bit row offsets.  Two launches, nothing
+ * allocated. */
+int icd_vae_ingest_f32(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first, const int32_t* h_count,
+                       const int32_t* h_coef, int32_t h_taps, const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef,
+                       int32_t v_taps, void* tmp, void* out, void* bytes, void* stream);
+/* Decoded images out of the VAE by diffusers' rule (VaeImageProcessor.postprocess, the SDXL samplers): x NCHW [B, 3, H, W] (fp16, or
+ * fp32 when is_f32) -> out uint8 NHWC [B, H, W, 3], the bytes of `(x / 2 + 0.5).clamp(0, 1)` followed by
+ * `(image.cpu().permute(0, 2, 3, 1).float().numpy() * 255).round().astype("uint8")`: x * 0.5, + 0.5, clamp to [0, 1], each evaluated in
+ * fp32 and rounded to x's dtype before the next step; then ONE fp32 product with 255.0f, rounded to the nearest integer with ties to even
+ * (icd_image_to_u8 truncates instead).  +-inf clamp to 255 / 0; NaN is outside the contract.  Any H, W; x aligned to its element, out
+ * 4-byte aligned.  One launch. */
+int icd_image_to_u8_round(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream);
 /* Streaming FID statistics: sum[d] += sum_i x[i][d], outer[a][b] += sum_i x[i][a] x[i][b] over the rows of x fp32 [n, D], in float64.
  * The thread that owns an output element starts from the stored value and adds the rows in index order: two calls give the bits of
  * one call on the concatenation, and sums of several calls (or ranks) simply add.  D % 4 == 0; x 16-byte aligned.  Two launches. */

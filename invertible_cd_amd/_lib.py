@@ -230,6 +230,9 @@ SIGNATURES = {
     "icd_vae_ingest": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
                        + [C.c_void_p] * 4),
     "icd_image_to_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icd_vae_ingest_f32": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32]
+                           + [C.c_void_p] * 4),
+    "icd_image_to_u8_round": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "icd_moments_f64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icd_profile_enable": (C.c_int, [C.c_int32]),
     "icd_profile_read": (C.c_int, [C.POINTER(ProfileRow), C.c_int32]),

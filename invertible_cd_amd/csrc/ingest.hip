@@ -5,8 +5,10 @@
 //   icd_image_resize_norm  LPIPS: both axes stretched to S x S, normalise, NHWC fp16 padded to 8 channels
 //   icd_fid_ingest         FID: resize + crop to uint8 (the bytes ToTensor sees), then bilinear to R x R and 2 u / 255 - 1, fp16 x 8
 //   icd_vae_ingest         VAE encoder: both axes stretched to S x S, u / 127.5 - 1, NHWC fp16 padded to 8 channels (+ the resized bytes)
-// All four share resample_h (the argument checks, the tables' descriptor, the horizontal pass); the vertical passes differ in what they
-// store.  icd_image_to_u8 is the way back: a decoded NCHW sample to uint8 NHWC.  Bandwidth kernels, 64-bit row offsets.
+//   icd_vae_ingest_f32     fp32-fidelity VAE encoder (SDXL): the same resize, 2 (u / 255) - 1 in fp32, split3 [hi | lo | hi] of 8 channels
+// All five share resample_h (the argument checks, the tables' descriptor, the horizontal pass); the vertical passes differ in what they
+// store.  icd_image_to_u8 (truncating, SD1.5) and icd_image_to_u8_round (half to even, SDXL) are the way back: a decoded NCHW sample
+// to uint8 NHWC.  Bandwidth kernels, 64-bit row offsets.
 #include "common.h"
 
 namespace {
@@ -154,6 +156,24 @@ struct StoreVae {                              // the VAE encoder's input: fp16(
     }
 };
 
+struct StoreVaeF32 {                           // the fp32-fidelity encoder's first operand: v = 2.0f * (fp32(u) / 255.0f) - 1.0f as diffusers'
+    unsigned char* bytes;                      // VaeImageProcessor.preprocess evaluates it (a division, a doubling, a subtraction), then the
+    __device__ void operator()(const PreK& p, long long it, const unsigned (&u)[3]) const {      // split of split_cast_kernel at scale 1:
+#pragma clang fp contract(off)
+        f16x8 hi = {0, 0, 0, 0, 0, 0, 0, 0}, lo = {0, 0, 0, 0, 0, 0, 0, 0};                       // hi = fp16(v), lo = fp16(v - hi); three
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                                                            // 16-byte stores [hi | lo | hi], pads zero
+            const float q = (float)u[c] / 255.0f;
+            const float v = 2.0f * q - 1.0f;
+            hi[c] = (half_t)v;
+            lo[c] = (half_t)(v - (float)hi[c]);
+        }
+        f16x8* o = reinterpret_cast<f16x8*>(p.out + it * 24);
+        o[0] = hi; o[1] = lo; o[2] = hi;
+        if (bytes) StoreBytes{bytes}(p, it, u);
+    }
+};
+
 // Vertical pass, no patches: one thread owns one output pixel, three byte columns of the horizontal pass's rows.
 template <typename Store>
 __global__ __launch_bounds__(256) void resample_v_pixel_kernel(PreK p, Store store) {
@@ -218,9 +238,20 @@ __device__ __forceinline__ unsigned sample_to_u8(T x) {
     return (unsigned)(int)(float)v;            // [0, 255]: truncation towards zero
 }
 
+// diffusers' VaeImageProcessor.postprocess: `(image / 2 + 0.5).clamp(0, 1)` in T as above, then `.float().numpy() * 255` - ONE fp32
+// product, not rounded to T - and `.round().astype("uint8")`: to nearest, ties to even.
+template <typename T>
+__device__ __forceinline__ unsigned sample_to_u8_round(T x) {
+#pragma clang fp contract(off)
+    T v = (T)((float)x * 0.5f);
+    v = (T)((float)v + 0.5f);
+    v = v < (T)0.f ? (T)0.f : (v > (T)1.f ? (T)1.f : v);
+    return (unsigned)(int)rintf((float)v * 255.0f);
+}
+
 // Decoded sample NCHW [B, 3, HW] -> uint8 NHWC [B, HW, 3].  One thread owns four consecutive pixels of the flattened batch (they may
 // straddle two samples when HW % 4 != 0) and stores their 12 bytes as three dwords; the last thread of an odd batch stores bytes.
-template <typename T>
+template <typename T, bool ROUND>
 __global__ __launch_bounds__(256) void image_to_u8_kernel(const T* x, long long npix, long long HW, unsigned char* out) {
     const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (p0 >= npix) return;
@@ -231,7 +262,7 @@ __global__ __launch_bounds__(256) void image_to_u8_kernel(const T* x, long long 
         const long long px = min(p0 + j, npix - 1), b = px / HW;
         const T* s = x + b * 2 * HW + px;                      // b * 3 HW + (px - b HW)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) u[j * 3 + c] = (unsigned char)sample_to_u8(s[c * HW]);
+        for (int c = 0; c < 3; ++c) u[j * 3 + c] = (unsigned char)(ROUND ? sample_to_u8_round(s[c * HW]) : sample_to_u8(s[c * HW]));
     }
     if (n == 4) {
         unsigned* o = reinterpret_cast<unsigned*>(out + p0 * 3);
@@ -384,17 +415,49 @@ extern "C" int icd_vae_ingest(const void* images, int32_t B, int32_t H, int32_t 
     return ICD_OK;
 }
 
-extern "C" int icd_image_to_u8(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream) {
-    ICD_CHECK_ARG(x && out, "icd_image_to_u8: null pointer");
-    ICD_CHECK_ARG(B > 0 && H > 0 && W > 0, "icd_image_to_u8: B, H, W must be positive (got %d, %d, %d)", B, H, W);
+extern "C" int icd_vae_ingest_f32(const void* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* h_first, const int32_t* h_count,
+                                  const int32_t* h_coef, int32_t h_taps, const int32_t* v_first, const int32_t* v_count, const int32_t* v_coef,
+                                  int32_t v_taps, void* tmp, void* out, void* bytes, void* stream) {
+    ICD_CHECK_ARG(images && tmp && out, "icd_vae_ingest_f32: null pointer");
+    ICD_CHECK_ARG(h_first && h_count && h_coef && v_first && v_count && v_coef, "icd_vae_ingest_f32: null coefficient table");
+    ICD_CHECK_ARG(B > 0, "icd_vae_ingest_f32: B must be positive (got %d)", B);
+    ICD_CHECK_ARG(H > 0 && W > 0, "icd_vae_ingest_f32: image sizes must be positive (got %d x %d)", H, W);
+    ICD_CHECK_ARG(S > 0 && S % 8 == 0 && S <= 4096, "icd_vae_ingest_f32: S must be a positive multiple of 8, <= 4096 (got %d)", S);
+    hipStream_t st = (hipStream_t)stream;
+    const long long vblocks = ((long long)B * S * S + 255) / 256;
+    const float mean[3] = {0.f, 0.f, 0.f}, stdv[3] = {1.f, 1.f, 1.f};           // unused: StoreVaeF32 spells its own arithmetic out
+    PreK p;
+    const int rc = resample_h("icd_vae_ingest_f32", 2.0, images, B, Axis{h_first, h_count, h_coef, h_taps, W, S, 0},
+                              Axis{v_first, v_count, v_coef, v_taps, H, S, 0}, S, 1, 24, mean, stdv, tmp, out, vblocks, st, p);
+    if (rc != ICD_OK) return rc;
+    hipLaunchKernelGGL(resample_v_pixel_kernel<StoreVaeF32>, dim3((unsigned)vblocks), dim3(256), 0, st, p, StoreVaeF32{(unsigned char*)bytes});
+    ICD_CHECK_LAUNCH("icd_vae_ingest_f32 (vertical)");
+    return ICD_OK;
+}
+
+namespace {
+// What the two output entries share, for the exported function `fn`: the checks and the launch of image_to_u8_kernel<T, ROUND>.
+template <bool ROUND>
+int image_to_u8(const char* fn, const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream) {
+    ICD_CHECK_ARG(x && out, "%s: null pointer", fn);
+    ICD_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: B, H, W must be positive (got %d, %d, %d)", fn, B, H, W);
     ICD_CHECK_ARG(((uintptr_t)x & (is_f32 ? 3 : 1)) == 0 && ((uintptr_t)out & 3) == 0,
-                  "icd_image_to_u8: x must be aligned to its element, out 4-byte aligned");
+                  "%s: x must be aligned to its element, out 4-byte aligned", fn);
     const long long HW = (long long)H * W, npix = (long long)B * HW;
     const long long blocks = ((npix + 3) / 4 + 255) / 256;
-    ICD_CHECK_ARG(blocks <= 0x7fffffffLL, "icd_image_to_u8: the batch exceeds the grid limit");
+    ICD_CHECK_ARG(blocks <= 0x7fffffffLL, "%s: the batch exceeds the grid limit", fn);
     hipStream_t st = (hipStream_t)stream;
-    if (is_f32) hipLaunchKernelGGL(image_to_u8_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, npix, HW, (unsigned char*)out);
-    else hipLaunchKernelGGL(image_to_u8_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const half_t*)x, npix, HW, (unsigned char*)out);
-    ICD_CHECK_LAUNCH("icd_image_to_u8");
+    if (is_f32) hipLaunchKernelGGL((image_to_u8_kernel<float, ROUND>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, npix, HW, (unsigned char*)out);
+    else hipLaunchKernelGGL((image_to_u8_kernel<half_t, ROUND>), dim3((unsigned)blocks), dim3(256), 0, st, (const half_t*)x, npix, HW, (unsigned char*)out);
+    ICD_CHECK_LAUNCH(fn);
     return ICD_OK;
+}
+}  // namespace
+
+extern "C" int icd_image_to_u8(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream) {
+    return image_to_u8<false>("icd_image_to_u8", x, is_f32, B, H, W, out, stream);
+}
+
+extern "C" int icd_image_to_u8_round(const void* x, int32_t is_f32, int32_t B, int32_t H, int32_t W, void* out, void* stream) {
+    return image_to_u8<true>("icd_image_to_u8_round", x, is_f32, B, H, W, out, stream);
 }

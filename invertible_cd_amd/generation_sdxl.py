@@ -225,8 +225,13 @@ def _expand_edit_latents(latents, batch_size, groups):
 # --------------------------------------------------------------------------------------------- forward (inversion)
 def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scales=50, num_inference_steps=1, timesteps=None,
                                  start_timestep=19, max_inverse_timestep_index=49, return_start_latent=False,
-                                 guidance_scale=None, compute_embeddings_fn=None, is_sdxl=False, inverse_endpoints=None, seed=0):
-    """Forward consistency model: image latents noised at timesteps[0] -> noise latents (utils/generation_sdxl.py:204-310)."""
+                                 guidance_scale=None, compute_embeddings_fn=None, is_sdxl=False, inverse_endpoints=None, seed=0, *,
+                                 resize_to=None):
+    """Forward consistency model: image latents noised at timesteps[0] -> noise latents (utils/generation_sdxl.py:204-310).
+
+    images may be uint8 [B, H, W, 3] on the device (or a list of such tensors of different sizes): pipe.prepare_latents resizes them there
+    to resize_to x resize_to (None: their own square size) and encodes them.  `images=<uint8 device tensor>, resize_to=1024` is the
+    device-route form of the reference driver's `Image.open(...).resize((1024, 1024))` + `preprocess` (running/sdxl/edit.py:198-199)."""
     if prompt is not None and isinstance(prompt, str):
         batch_size = 1
     elif prompt is not None and isinstance(prompt, list):
@@ -247,8 +252,9 @@ def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scale
 
     alpha_schedule = torch.sqrt(pipe.scheduler.alphas_cumprod).cpu()
     sigma_schedule = torch.sqrt(1 - pipe.scheduler.alphas_cumprod).cpu()
+    kw = {} if resize_to is None else {'resize_to': resize_to}
     start_latents = pipe.prepare_latents(images, timesteps[0], batch_size, 1, prompt_embeds.dtype, device,
-                                         generator=torch.Generator().manual_seed(seed))
+                                         generator=torch.Generator().manual_seed(seed), **kw)
     latents = start_latents.clone()
     w_embedding = None if guidance_scale is None else _w_embedding([guidance_scale] * batch_size, latents.device, latents.dtype)
     ptype = pipe.scheduler.config.prediction_type
@@ -265,8 +271,11 @@ def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scale
 def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=50, num_inference_steps=1, timesteps=None,
                          start_timestep=19, max_inverse_timestep_index=49, return_latent=False, guidance_scale=None,
                          compute_embeddings_fn=None, is_sdxl=False, endpoints=None, use_dynamic_guidance=False, tau1=0.7,
-                         tau2=0.7, amplify_prompt=None, *, controller=None):
+                         tau2=0.7, amplify_prompt=None, *, controller=None, output_type='pil'):
     """Reverse consistency model: noise latents -> image (utils/generation_sdxl.py:324-473).
+
+    output_type: 'pil' (the reference), 'pt' (the denormalised tensor) or 'uint8_device' - the PIL images' bytes as one uint8
+    [B, H, W, 3] tensor that never leaves the device (np.stack([np.array(im) for im in <the 'pil' result>])); metrics.py scores it there.
 
     controller (beyond the reference, whose SDXL scripts register none): a p2p controller - make_controller(...), AttentionStore, a
     ControllerBatch - turns the call into a prompt-to-prompt edit of the batch [source, edit_1, ...].  It is registered on pipe.unet
@@ -275,6 +284,9 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
     precision level.  `latents` may be one [1, 4, h, w] sample (usually inverse_sample_deterministic's output), expanded over the prompts.
     Prompt groups as in generation.runner: `prompt` a list of G lists of P prompts with a p2p.ControllerBatch of G members, latents
     [G, 4, h, w] (each repeated over its group) or [G * P, 4, h, w]."""
+    from .pipelines import OUTPUT_TYPES
+    if output_type not in OUTPUT_TYPES:
+        raise ValueError(f"sample_deterministic: output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
     groups = None
     if controller is not None:
         from . import p2p
@@ -354,5 +366,5 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
     else:
         vae.to(torch.float32)
         image = vae.decode(latents.to(torch.float32) / vae.config.scaling_factor, return_dict=False)[0]
-        image = pipe.image_processor.postprocess(image, output_type="pil", do_denormalize=[True] * image.shape[0])
+        image = pipe.image_processor.postprocess(image, output_type=output_type, do_denormalize=[True] * image.shape[0])
     return (image, latents) if return_latent else image

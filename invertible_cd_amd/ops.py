@@ -756,6 +756,32 @@ def image_to_u8(image):
     return out
 
 
+def vae_ingest_f32(images, size, want_bytes=False):
+    """uint8 NHWC images [B, H, W, 3] on the device -> (fp16 [B * size * size, 24], uint8 [B, size, size, 3] or None): Pillow's BICUBIC
+    resize as in vae_ingest, then diffusers' VaeImageProcessor.preprocess in fp32, `2.0 * (u / 255.0) - 1.0`, as the split3 operand
+    [hi | lo | hi] of the 8-channel packing - the bits of split_cast on AutoencoderKL._pack32's tensor (icd_vae_ingest_f32)."""
+    B, H, W = _chk_images(images, "vae_ingest_f32")
+    tmp = torch.empty((B * H, size, 3), device=images.device, dtype=torch.uint8)
+    out = torch.empty((B * size * size, 24), device=images.device, dtype=torch.float16)
+    bytes_out = torch.empty((B, size, size, 3), device=images.device, dtype=torch.uint8) if want_bytes else None
+    _lib.check(_lib.load().icd_vae_ingest_f32(_p(images), B, H, W, size, *_table_args(W, size, H, size, images.device), _p(tmp), _p(out),
+                                              _p(bytes_out), _stream()), "icd_vae_ingest_f32")
+    return out, bytes_out
+
+
+def image_to_u8_round(image):
+    """decoded sample NCHW [B, 3, H, W] (contiguous cuda fp16 / fp32) -> uint8 NHWC [B, H, W, 3]: the bytes of diffusers'
+    VaeImageProcessor.postprocess, `(image / 2 + 0.5).clamp(0, 1)` in the sample's own dtype, then
+    `(... .float().numpy() * 255).round().astype("uint8")` - rounded half to even where image_to_u8 truncates (icd_image_to_u8_round)."""
+    assert image.is_cuda and image.dim() == 4 and image.shape[1] == 3 and image.is_contiguous() \
+        and image.dtype in (torch.float16, torch.float32), "image_to_u8_round: need a contiguous cuda fp16 / fp32 [B, 3, H, W] tensor"
+    B, _, H, W = image.shape
+    out = torch.empty((B, H, W, 3), device=image.device, dtype=torch.uint8)
+    _lib.check(_lib.load().icd_image_to_u8_round(_p(image), int(image.dtype == torch.float32), B, H, W, _p(out), _stream()),
+               "icd_image_to_u8_round")
+    return out
+
+
 def relu(x, inplace=False):
     _chk16(x, "x")
     out = x if inplace else torch.empty_like(x)

@@ -31,8 +31,21 @@ class StableDiffusionPipeline:
         return self
 
 
+OUTPUT_TYPES = ("pil", "pt", "uint8_device")
+
+
 class _ImageProcessor:
     def postprocess(self, image, output_type="pil", do_denormalize=None):
+        """'pil': diffusers' VaeImageProcessor.postprocess; 'uint8_device': the same bytes, np.stack([np.array(im) for im in <the PIL
+        result>]), as one uint8 [B, H, W, 3] tensor left on the device (icd_image_to_u8_round; the name is generation.runner's
+        return_type, metrics.py takes the tensor as it is); anything else: the denormalised tensor, as before."""
+        if output_type == "uint8_device":
+            if not image.is_cuda:
+                raise ValueError("postprocess: output_type='uint8_device' needs the image on the device")
+            from . import ops
+            if image.dtype not in (torch.float16, torch.float32):
+                image = image.float()
+            return ops.image_to_u8_round(image.contiguous())
         image = (image / 2 + 0.5).clamp(0, 1)
         if output_type != "pil":
             return image
@@ -152,24 +165,57 @@ class StableDiffusionXLPipeline:
         return rep(emb.to(self.unet.dtype)), rep(None if neg is None else neg.to(self.unet.dtype)), rep(pooled), rep(neg_pooled)
 
 
+def _uint8_images(image, resize_to):
+    """The uint8 images of prepare_latents' device route as a list, or None when `image` is anything else (PIL, float tensors, numpy).
+    uint8 tensors that the device route cannot take are refused here, before any GPU work: no other route takes them."""
+    items = [image] if torch.is_tensor(image) else (list(image) if isinstance(image, (list, tuple)) else [])
+    if not items or not all(torch.is_tensor(i) for i in items) or not any(i.dtype == torch.uint8 for i in items):
+        if resize_to is not None:
+            raise ValueError("prepare_latents: resize_to applies to uint8 device images only")
+        return None
+    for i in items:
+        if i.dtype != torch.uint8 or i.dim() not in (3, 4) or i.shape[-1] != 3:
+            raise ValueError(f"prepare_latents: uint8 images must be [B, H, W, 3] or [H, W, 3] tensors, got {i.dtype} {tuple(i.shape)}")
+    if resize_to is None:
+        sizes = sorted({tuple(i.shape[-3:-1]) for i in items})
+        if len(sizes) != 1 or sizes[0][0] != sizes[0][1]:
+            raise ValueError(f"prepare_latents: resize_to=None takes square images of one size, got (H, W) = {sizes}: pass resize_to")
+    elif resize_to <= 0 or resize_to % 8:
+        raise ValueError(f"prepare_latents: resize_to must be a positive multiple of 8, got {resize_to}")
+    if not all(i.is_cuda for i in items):
+        raise ValueError("prepare_latents: uint8 images are taken on the device only, got a host tensor: move it with .to('cuda'), "
+                         "or pass PIL images / a float [B, 3, H, W] tensor for the host route")
+    return items
+
+
 class StableDiffusionXLImg2ImgPipeline(StableDiffusionXLPipeline):
     def prepare_latents(self, image, timestep, batch_size, num_images_per_prompt, dtype, device, generator=None,
-                        add_noise=True):
+                        add_noise=True, *, resize_to=None):
         """diffusers 0.25.1 StableDiffusionXLImg2ImgPipeline.prepare_latents, the call of utils/generation_sdxl.py:273-276:
         image (PIL / list / [B,3,H,W] in [-1,1]) -> VAE encode in fp32 -> latent_dist.sample(generator) * scaling_factor
         (4-channel inputs are taken as latents), repeated to batch_size, + add_noise(randn, timestep).  Both draws come
-        from `generator` in this order, as in diffusers."""
-        if not torch.is_tensor(image):
-            image = self.image_processor.preprocess(image)
-        image = image.to(device=device, dtype=dtype)
+        from `generator` in this order, as in diffusers.
+        Device route: a uint8 [B, H, W, 3] tensor on the device, or a list of such tensors whose sizes may differ, is resized there to
+        resize_to x resize_to like PIL.Image.resize (None: the images' own, common, square size) and encoded by
+        vae.encode_images(rule='image_processor', image_dtype=dtype): the latents the host route gives for `preprocess` of the resized
+        PIL images, its cast to `dtype` in front of the upcast included.  Everything after the encode is shared."""
+        u8 = _uint8_images(image, resize_to)
+        if u8 is None:
+            if not torch.is_tensor(image):
+                image = self.image_processor.preprocess(image)
+            image = image.to(device=device, dtype=dtype)
         batch_size = batch_size * num_images_per_prompt
-        if image.shape[1] == 4:
+        if u8 is None and image.shape[1] == 4:
             init = image
         else:
             if self.vae is None:
                 raise RuntimeError("no VAE attached: pass 4-channel latents or attach a VAE (components['vae_state_dict'])")
             self.vae.to(torch.float32)                       # force_upcast, as diffusers does for the SDXL VAE
-            init = self.vae.encode(image.float()).latent_dist.sample(generator)
+            if u8 is None:
+                dist = self.vae.encode(image.float()).latent_dist
+            else:
+                dist = self.vae.encode_images(u8, resize_to, rule='image_processor', image_dtype=dtype).latent_dist
+            init = dist.sample(generator)
             self.vae.to(dtype)
             init = init.to(dtype) * self.vae.config.scaling_factor
         if batch_size > init.shape[0]:

@@ -399,9 +399,13 @@ class AutoencoderKL:
                             cout=cfg.out_channels)
 
     def _encode_chunk32(self, img):
-        w, ws, cfg = self.w, self._split_weights(), self.cfg
         B, _, H, W = img.shape
-        x = ops.conv3x3(self._pack32(img), B, H, W, ws["encoder.conv_in.weight"], w["encoder.conv_in.bias"], out_f32=True)
+        return self._encode_split32(self._pack32(img), B, H, W)
+
+    def _encode_split32(self, x, B, H, W):
+        """x: the split3 fp16 [B * H * W, 24] operand of conv_in (_pack32's tensor, or icd_vae_ingest_f32's)"""
+        w, ws, cfg = self.w, self._split_weights(), self.cfg
+        x = ops.conv3x3(x, B, H, W, ws["encoder.conv_in.weight"], w["encoder.conv_in.bias"], out_f32=True)
         nb = len(cfg.block_out_channels)
         for i in range(nb):
             for j in range(cfg.layers_per_block):
@@ -523,14 +527,27 @@ class AutoencoderKL:
         return _Out(latent_dist=dist) if return_dict else (dist,)
 
     @torch.no_grad()
-    def encode_images(self, images_u8, size=None, want_bytes=False, return_dict=True):
+    def encode_images(self, images_u8, size=None, want_bytes=False, return_dict=True, *, rule='load_512', image_dtype=torch.float32):
         """Real images straight into the encoder: uint8 NHWC on the device, [B, H, W, 3] or a list of [H, W, 3] / [b, H, W, 3] tensors
         whose sizes may differ, resized like np.array(PIL.Image.resize((size, size))) (size=None: their own, common, square size) ->
         latent_dist, the bits `encode` gives the host route's `torch.from_numpy(arr).float() / 127.5 - 1` of the resized arrays.
         fp16: icd_vae_ingest writes conv_in's input.  fp32 fidelity: the resized bytes go through the host route's own fp32 values (a
         256-entry table evaluated by that very expression on the host) into _encode_chunk32.  The images are ingested size by size and
         encoded in the caller's order, max_chunk at a time like `encode`.  want_bytes: the result also carries the resized bytes as
-        ['images'], uint8 [B, size, size, 3]."""
+        ['images'], uint8 [B, size, size, 3].
+        rule='image_processor' (fp32 fidelity only; the SDXL route): the same resize, then diffusers' VaeImageProcessor.preprocess,
+        `2.0 * (u / 255.0) - 1.0` in fp32 - the bits `encode` gives `preprocess` of the resized PIL images.  icd_vae_ingest_f32 writes
+        conv_in's split operand itself: no fp32 image, no lookup, no cast pass.  image_dtype=torch.float16 (this rule only): the bits
+        `encode` gives `preprocess(...).half().float()`, the image as a pipeline that runs in fp16 hands it over (diffusers' img2img
+        prepare_latents casts to the pipeline's dtype before it upcasts): fp16(v) is the operand's hi half, so its lo half is zero."""
+        if rule not in ('load_512', 'image_processor'):
+            raise ValueError(f"AutoencoderKL.encode_images: rule must be 'load_512' or 'image_processor', got {rule!r}")
+        processor = rule == 'image_processor'
+        if image_dtype not in (torch.float16, torch.float32) or (image_dtype != torch.float32 and not processor):
+            raise ValueError(f"AutoencoderKL.encode_images: image_dtype is float32, or float16 with rule='image_processor', got {image_dtype}")
+        if processor and self.dtype != torch.float32:
+            raise ValueError("AutoencoderKL.encode_images: rule='image_processor' needs the fp32-fidelity mode (vae.to(torch.float32)), "
+                             f"this VAE is {self.dtype}")
         groups = [images_u8] if isinstance(images_u8, torch.Tensor) else list(images_u8)
         groups = [g[None] if g.dim() == 3 else g for g in groups]
         for g in groups:
@@ -552,7 +569,12 @@ class AutoencoderKL:
         x8, u8 = {}, {}
         for idx in by_size.values():
             g = groups[idx[0]] if len(idx) == 1 else torch.cat([groups[i] for i in idx])
-            a, b = ops.vae_ingest(g.contiguous(), size, want_bytes=want_bytes or f32)
+            if processor:
+                a, b = ops.vae_ingest_f32(g.contiguous(), size, want_bytes=want_bytes)
+                if image_dtype == torch.float16:
+                    a[:, 8:16].zero_()                           # [hi | lo | hi]: an fp16 image has no lo half
+            else:
+                a, b = ops.vae_ingest(g.contiguous(), size, want_bytes=want_bytes or f32)
             r0 = 0
             for i in idx:
                 n = groups[i].shape[0]
@@ -562,11 +584,13 @@ class AutoencoderKL:
         x8 = x8[0] if one else torch.cat([x8[i] for i in range(len(groups))])
         u8 = None if u8[0] is None else (u8[0] if one else torch.cat([u8[i] for i in range(len(groups))]))
         B, outs = x8.shape[0] // (size * size), []
-        if f32:
+        if f32 and not processor:
             lut = (torch.arange(256, dtype=torch.uint8).float() / 127.5 - 1).to(self.device)          # the host route's values, exactly
         for i in range(0, B, self.max_chunk):
             n = min(self.max_chunk, B - i)
-            if f32:
+            if processor:
+                outs.append(self._encode_split32(x8[i * size * size:(i + n) * size * size], n, size, size))
+            elif f32:
                 outs.append(self._encode_chunk32(lut[u8[i:i + n].long()].permute(0, 3, 1, 2).contiguous()))
             else:
                 outs.append(self._encode_packed(x8[i * size * size:(i + n) * size * size], n, size, size))
