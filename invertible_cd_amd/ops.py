@@ -759,7 +759,7 @@ def image_to_u8(image):
 def vae_ingest_f32(images, size, want_bytes=False):
     """uint8 NHWC images [B, H, W, 3] on the device -> (fp16 [B * size * size, 24], uint8 [B, size, size, 3] or None): Pillow's BICUBIC
     resize as in vae_ingest, then diffusers' VaeImageProcessor.preprocess in fp32, `2.0 * (u / 255.0) - 1.0`, as the split3 operand
-    [hi | lo | hi] of the 8-channel packing - the bits of split_cast on AutoencoderKL._pack32's tensor (icd_vae_ingest_f32)."""
+    [hi | lo | hi] of the 8-channel packing - the bits of split_cast on vae._pack32's tensor (icd_vae_ingest_f32)."""
     B, H, W = _chk_images(images, "vae_ingest_f32")
     tmp = torch.empty((B * H, size, 3), device=images.device, dtype=torch.uint8)
     out = torch.empty((B * size * size, 24), device=images.device, dtype=torch.float16)

@@ -28,6 +28,12 @@ Two arithmetic modes, selected like the reference does it, through `vae.to(dtype
     power of two chosen from their max |x| (icd_absmax) on the way to fp16 and the conv's alpha restores the scale exactly
     (icd_split_cast).  Only the
     mid-block attention keeps fp16 q / k / v / P (bounded by construction: they follow a GroupNorm and a softmax).
+Layout of this file.  The topology exists once: VAEConfig.levels enumerates the blocks (for state_dict_shapes and the walks), and
+AutoencoderKL._resnet / _attention / _mid / _decode_body / _encode_body walk them in an arithmetic object, _Fp16Carry or _Fp32Split,
+that AutoencoderKL._arithmetic picks once per call from `dtype`.  The two differ only in what a residual stream is, the GroupNorm that
+reads it, how a launch that produces a stream or reads the raw stream is issued, the weight dictionary, the pack of the first operand and
+the upsampler (phase form in fp16 only).  The folds exist once too: _fold_state_dict gives fp32 masters under the kernels' keys;
+pack_vae_state_dict (fp16, at load) and _split_vae_weights (split3, on the first fp32 use, from the retained state dict) map over them.
 """
 from dataclasses import dataclass, replace
 from types import SimpleNamespace
@@ -54,9 +60,23 @@ class VAEConfig:
         """Reduced-width copy (tests): channel counts must stay multiples of 32 (GroupNorm groups) ."""
         return replace(self, block_out_channels=tuple(block_out_channels))
 
+    def levels(self, side):
+        """The resolution levels of one side, "encoder" or "decoder", in execution order: ([(resnet prefix, cin, cout), ...], prefix of
+        the Down/Upsample2D conv that ends the level or None, the level's channels).  The one place that knows the block key strings."""
+        enc = side == "encoder"
+        ch = list(self.block_out_channels) if enc else list(self.block_out_channels)[::-1]
+        blocks, resample = ("down_blocks", "downsamplers") if enc else ("up_blocks", "upsamplers")
+        cin = ch[0]
+        for i, c in enumerate(ch):
+            resnets = []
+            for j in range(self.layers_per_block + (not enc)):
+                resnets.append((f"{side}.{blocks}.{i}.resnets.{j}.", cin, c))
+                cin = c
+            yield resnets, f"{side}.{blocks}.{i}.{resample}.0.conv." if i < len(ch) - 1 else None, c
+
     def state_dict_shapes(self):
         """diffusers AutoencoderKL keys -> shapes (same layout the oracle pins by the exact SD VAE parameter count)."""
-        ch, L, zc = list(self.block_out_channels), self.layers_per_block, self.latent_channels
+        ch, zc = list(self.block_out_channels), self.latent_channels
         out = {}
 
         def resnet(p, cin, cout):
@@ -75,15 +95,15 @@ class VAEConfig:
                 out[a + n + ".weight"] = (c, c); out[a + n + ".bias"] = (c,)
             resnet(p + "resnets.1.", c, c)
 
+        def levels(side):
+            for resnets, resample, c in self.levels(side):
+                for p, cin, cout in resnets:
+                    resnet(p, cin, cout)
+                if resample:
+                    out[resample + "weight"] = (c, c, 3, 3); out[resample + "bias"] = (c,)
+
         out["encoder.conv_in.weight"] = (ch[0], self.in_channels, 3, 3); out["encoder.conv_in.bias"] = (ch[0],)
-        cin = ch[0]
-        for i, c in enumerate(ch):
-            for j in range(L):
-                resnet(f"encoder.down_blocks.{i}.resnets.{j}.", cin, c)
-                cin = c
-            if i < len(ch) - 1:
-                out[f"encoder.down_blocks.{i}.downsamplers.0.conv.weight"] = (c, c, 3, 3)
-                out[f"encoder.down_blocks.{i}.downsamplers.0.conv.bias"] = (c,)
+        levels("encoder")
         mid("encoder.mid_block.", ch[-1])
         out["encoder.conv_norm_out.weight"] = (ch[-1],); out["encoder.conv_norm_out.bias"] = (ch[-1],)
         out["encoder.conv_out.weight"] = (2 * zc, ch[-1], 3, 3); out["encoder.conv_out.bias"] = (2 * zc,)
@@ -92,14 +112,7 @@ class VAEConfig:
         rev = ch[::-1]
         out["decoder.conv_in.weight"] = (rev[0], zc, 3, 3); out["decoder.conv_in.bias"] = (rev[0],)
         mid("decoder.mid_block.", rev[0])
-        cin = rev[0]
-        for i, c in enumerate(rev):
-            for j in range(L + 1):
-                resnet(f"decoder.up_blocks.{i}.resnets.{j}.", cin, c)
-                cin = c
-            if i < len(rev) - 1:
-                out[f"decoder.up_blocks.{i}.upsamplers.0.conv.weight"] = (c, c, 3, 3)
-                out[f"decoder.up_blocks.{i}.upsamplers.0.conv.bias"] = (c,)
+        levels("decoder")
         out["decoder.conv_norm_out.weight"] = (rev[-1],); out["decoder.conv_norm_out.bias"] = (rev[-1],)
         out["decoder.conv_out.weight"] = (self.out_channels, rev[-1], 3, 3); out["decoder.conv_out.bias"] = (self.out_channels,)
         return out
@@ -143,6 +156,42 @@ class LatentDist:
         return self.mean + self.std * noise
 
 
+def _pad(t, n, dim=0):
+    """t zero-padded to n along dim"""
+    out = torch.zeros(*t.shape[:dim], n, *t.shape[dim + 1:])
+    out.narrow(dim, 0, t.shape[dim]).copy_(t)
+    return out
+
+
+def _fold_state_dict(cfg: VAEConfig, sd):
+    """diffusers-layout AutoencoderKL state dict -> fp32 masters on the host under the kernels' keys, the module docstring's folds applied:
+    convs [O, I, kh, kw] (the first convs padded to 8 input channels, the last ones to 4 outputs), projections [O, I], biases / affine."""
+    f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
+    zc = cfg.latent_channels
+    folded = ("quant_conv.", "post_quant_conv.", "encoder.conv_out.", "decoder.conv_out.")
+    M = {k: f32(k) for k in cfg.state_dict_shapes() if not k.startswith(folded) and ".attentions.0.to_" not in k}
+    for a in ("encoder.mid_block.attentions.0.", "decoder.mid_block.attentions.0."):
+        M[a + "to_qk.weight"] = torch.cat([f32(a + "to_q.weight"), f32(a + "to_k.weight")])
+        M[a + "to_qk.bias"] = torch.cat([f32(a + "to_q.bias"), f32(a + "to_k.bias")])
+        M[a + "to_v.weight"] = f32(a + "to_v.weight")
+        wo = M[a + "to_out.weight"] = f32(a + "to_out.0.weight")
+        M[a + "to_out.bias"] = wo @ f32(a + "to_v.bias") + f32(a + "to_out.0.bias")             # softmax rows sum to one
+    M["encoder.conv_in.weight"] = _pad(M["encoder.conv_in.weight"], 8, dim=1)
+    wq, bq = f32("quant_conv.weight").reshape(2 * zc, 2 * zc), f32("quant_conv.bias")
+    wo, bo = f32("encoder.conv_out.weight"), f32("encoder.conv_out.bias")
+    for name, r in (("mean", slice(0, zc)), ("logvar", slice(zc, None))):    # rows of quant_conv(conv_out(.)): latent_dist.mean / .std
+        M[f"encoder.conv_out_{name}.weight"] = _pad(torch.einsum("om,mchw->ochw", wq[r], wo), 4)
+        M[f"encoder.conv_out_{name}.bias"] = _pad(wq[r] @ bo + bq[r], 4)
+    wpq, bpq = f32("post_quant_conv.weight").reshape(zc, zc), f32("post_quant_conv.bias")
+    wi = M["decoder.conv_in.weight"]
+    w8 = torch.zeros(wi.shape[0], 8, 3, 3)
+    w8[:, :zc] = torch.einsum("ochw,cd->odhw", wi, wpq)
+    w8[:, zc] = torch.einsum("ochw,c->ohw", wi, bpq)                          # rides on the ones channel
+    M["decoder.conv_in.weight"] = w8
+    M["decoder.conv_out.weight"], M["decoder.conv_out.bias"] = _pad(f32("decoder.conv_out.weight"), 4), _pad(f32("decoder.conv_out.bias"), 4)
+    return M
+
+
 def pack_vae_state_dict(cfg: VAEConfig, sd, device="cuda"):
     """diffusers-layout AutoencoderKL state dict -> kernel layout (fp16 weights, fp32 biases / affine)."""
     missing = [k for k in cfg.state_dict_shapes() if k not in sd]
@@ -151,78 +200,109 @@ def pack_vae_state_dict(cfg: VAEConfig, sd, device="cuda"):
     for k, shp in cfg.state_dict_shapes().items():
         if tuple(sd[k].shape) != tuple(shp):
             raise ValueError(f"{k}: expected shape {tuple(shp)}, got {tuple(sd[k].shape)}")
-    f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
+    from .unet import upsample_phase_weights
     P = {}
-    half = lambda t: t.to(device=device, dtype=torch.float16).contiguous()
-    full = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
-
-    def resnet(p):
-        for n in ("norm1", "norm2"):
-            P[p + n + ".weight"], P[p + n + ".bias"] = full(f32(p + n + ".weight")), full(f32(p + n + ".bias"))
-        for n in ("conv1", "conv2"):
-            P[p + n + ".weight"], P[p + n + ".bias"] = half(ops.pack_conv_weight(f32(p + n + ".weight"))), full(f32(p + n + ".bias"))
-        if p + "conv_shortcut.weight" in sd:
-            w = f32(p + "conv_shortcut.weight")
-            P[p + "conv_shortcut.weight"], P[p + "conv_shortcut.bias"] = half(w.reshape(w.shape[0], -1)), full(f32(p + "conv_shortcut.bias"))
-
-    def mid(p):
-        resnet(p + "resnets.0."); resnet(p + "resnets.1.")
-        a = p + "attentions.0."
-        P[a + "group_norm.weight"], P[a + "group_norm.bias"] = full(f32(a + "group_norm.weight")), full(f32(a + "group_norm.bias"))
-        P[a + "to_qk.weight"] = half(torch.cat([f32(a + "to_q.weight"), f32(a + "to_k.weight")]))
-        P[a + "to_qk.bias"] = full(torch.cat([f32(a + "to_q.bias"), f32(a + "to_k.bias")]))
-        P[a + "to_v.weight"] = half(f32(a + "to_v.weight"))
-        wo = f32(a + "to_out.0.weight")
-        P[a + "to_out.weight"] = half(wo)
-        P[a + "to_out.bias"] = full(wo @ f32(a + "to_v.bias") + f32(a + "to_out.0.bias"))      # softmax rows sum to one
-
-    ch, L, zc = list(cfg.block_out_channels), cfg.layers_per_block, cfg.latent_channels
-    # ---- encoder
-    w = f32("encoder.conv_in.weight")
-    w8 = torch.zeros(w.shape[0], 8, 3, 3); w8[:, :cfg.in_channels] = w
-    P["encoder.conv_in.weight"], P["encoder.conv_in.bias"] = half(ops.pack_conv_weight(w8)), full(f32("encoder.conv_in.bias"))
-    for i in range(len(ch)):
-        for j in range(L):
-            resnet(f"encoder.down_blocks.{i}.resnets.{j}.")
-        if i < len(ch) - 1:
-            k = f"encoder.down_blocks.{i}.downsamplers.0.conv."
-            P[k + "weight"], P[k + "bias"] = half(ops.pack_conv_weight(f32(k + "weight"))), full(f32(k + "bias"))
-    mid("encoder.mid_block.")
-    P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"] = full(f32("encoder.conv_norm_out.weight")), full(f32("encoder.conv_norm_out.bias"))
-    wq, bq = f32("quant_conv.weight").reshape(2 * zc, 2 * zc), f32("quant_conv.bias")
-    wo, bo = f32("encoder.conv_out.weight"), f32("encoder.conv_out.bias")
-    wm = torch.einsum("om,mchw->ochw", wq[:zc], wo)                          # mean rows of quant_conv(conv_out(.))
-    w4 = torch.zeros(4, wo.shape[1], 3, 3); w4[:zc] = wm
-    b4 = torch.zeros(4); b4[:zc] = wq[:zc] @ bo + bq[:zc]
-    P["encoder.conv_out_mean.weight"], P["encoder.conv_out_mean.bias"] = half(ops.pack_conv_weight(w4)), full(b4)
-    wl = torch.einsum("om,mchw->ochw", wq[zc:], wo)                          # log-variance rows (latent_dist.sample / .std)
-    w4 = torch.zeros(4, wo.shape[1], 3, 3); w4[:zc] = wl
-    b4 = torch.zeros(4); b4[:zc] = wq[zc:] @ bo + bq[zc:]
-    P["encoder.conv_out_logvar.weight"], P["encoder.conv_out_logvar.bias"] = half(ops.pack_conv_weight(w4)), full(b4)
-    # ---- decoder
-    wpq, bpq = f32("post_quant_conv.weight").reshape(zc, zc), f32("post_quant_conv.bias")
-    wi = f32("decoder.conv_in.weight")
-    w8 = torch.zeros(wi.shape[0], 8, 3, 3)
-    w8[:, :zc] = torch.einsum("ochw,cd->odhw", wi, wpq)
-    w8[:, zc] = torch.einsum("ochw,c->ohw", wi, bpq)                          # rides on the ones channel
-    P["decoder.conv_in.weight"], P["decoder.conv_in.bias"] = half(ops.pack_conv_weight(w8)), full(f32("decoder.conv_in.bias"))
-    mid("decoder.mid_block.")
-    for i in range(len(ch)):
-        for j in range(L + 1):
-            resnet(f"decoder.up_blocks.{i}.resnets.{j}.")
-        if i < len(ch) - 1:
-            k = f"decoder.up_blocks.{i}.upsamplers.0.conv."
-            P[k + "weight"], P[k + "bias"] = half(ops.pack_conv_weight(f32(k + "weight"))), full(f32(k + "bias"))
+    for k, t in _fold_state_dict(cfg, sd).items():
+        if t.dim() == 1:                                                      # a bias or a GroupNorm's affine
+            P[k] = t.to(device=device, dtype=torch.float32).contiguous()
+            continue
+        P[k] = (ops.pack_conv_weight(t) if t.dim() == 4 else t).to(device=device, dtype=torch.float16).contiguous()
+        if ".upsamplers." in k:
             # the phase form of Upsample2D (four 2 x 2 convs on the input grid with tap-summed weights: 4/9 of the flops, unet.py)
-            from .unet import upsample_phase_weights
-            for ph, wp in enumerate(upsample_phase_weights(f32(k + "weight"))):
-                P[k + f"phase.{ph}"] = half(wp.reshape(wp.shape[0], -1).contiguous())
-    P["decoder.conv_norm_out.weight"], P["decoder.conv_norm_out.bias"] = full(f32("decoder.conv_norm_out.weight")), full(f32("decoder.conv_norm_out.bias"))
-    wo, bo = f32("decoder.conv_out.weight"), f32("decoder.conv_out.bias")
-    w4 = torch.zeros(4, wo.shape[1], 3, 3); w4[:cfg.out_channels] = wo
-    b4 = torch.zeros(4); b4[:cfg.out_channels] = bo
-    P["decoder.conv_out.weight"], P["decoder.conv_out.bias"] = half(ops.pack_conv_weight(w4)), full(b4)
+            for ph, wp in enumerate(upsample_phase_weights(t)):
+                P[k[:-len("weight")] + f"phase.{ph}"] = wp.reshape(wp.shape[0], -1).to(device=device, dtype=torch.float16).contiguous()
     return P
+
+
+def _split_vae_weights(M, device):
+    """[w_hi | w_hi | w_lo] per tap, from the fp32 masters, for every conv / projection whose input is a split3 tensor"""
+    S = {}
+    for k, t in M.items():
+        if t.dim() == 4:
+            S[k] = ops.split_weight(t.permute(0, 2, 3, 1)).reshape(t.shape[0], -1).to(device)          # [O, taps * 3I]
+        elif k.endswith(("to_qk.weight", "to_v.weight")):
+            S[k] = ops.split_weight(t).to(device)
+    return S
+
+
+def _pack32(x_nchw, device, ones_channel=-1):
+    """NCHW fp32 (<= 8 channels) -> split3 [B*H*W, 24] of the 8-channel token-major packing (data movement + split only)."""
+    B, Cc, H, W = x_nchw.shape
+    t = torch.zeros((B, H, W, 8), device=device, dtype=torch.float32)
+    t[..., :Cc] = x_nchw.to(device, torch.float32).permute(0, 2, 3, 1)
+    if ones_channel >= 0:
+        t[..., ones_channel] = 1.0
+    return ops.split_cast(t.reshape(B * H * W, 8), 1.0)
+
+
+# The two arithmetics the one topology walk of AutoencoderKL runs in.  Each says what a residual stream is and supplies: `w` / `ws` (biases,
+# affine and the plain fp16 weights / the weights its operands multiply), pack (the first operand), norm (a GroupNorm of the stream -> an
+# operand), issue (a conv or GEMM whose result is a stream, with an optional stream as residual), raw (the stream itself as an operand, with
+# the launch arguments that undo what that took) and upsample.  `rows` is the row count of issue's result.
+class _Fp16Carry:
+    """A stream is the pair (x, xc): fp16 token-major x and the rounding error of its last x <- x + f(x) in one bf8 byte per element
+    (icd_gemm_desc.resid_carry / out_carry, the UNet's residual mode 2); every GroupNorm normalises fp16 + carry (icd_groupnorm_carry), so
+    the stream behaves like a 14-bit-mantissa tensor.  xc None (always, with carry=False): the plain fp16 stream."""
+    out_dtype = torch.float16
+
+    def __init__(self, w, groups, carry, upsample_phases):
+        self.w = self.ws = w
+        self.groups, self.carry, self.upsample_phases = groups, carry, upsample_phases
+
+    def pack(self, x_nchw, ones_channel=-1):
+        return ops.pack_nchw(x_nchw, ones_channel=ones_channel)
+
+    def norm(self, s, B, HW, k, silu):
+        (x, xc), w = s, self.w
+        if xc is None:
+            return ops.groupnorm(x, B, HW, w[k + "weight"], w[k + "bias"], EPS, silu, groups=self.groups)
+        return ops.groupnorm_carry(x, B, HW, w[k + "weight"], w[k + "bias"], EPS, silu, carry=xc, groups=self.groups)
+
+    def _oc(self, rows, cols, like):
+        return torch.empty((rows, cols), device=like.device, dtype=torch.uint8) if self.carry else None
+
+    def issue(self, fn, a, geom, weight, bias, rows, resid=(None, None), **kw):
+        oc = self._oc(rows, weight.shape[0], a)
+        return fn(a, *geom, weight, bias, resid=resid[0], resid_carry=resid[1], out_carry=oc, **kw), oc
+
+    def raw(self, s):
+        return s[0], {}
+
+    def upsample(self, s, B, H, W, k):
+        """Upsample2D as four 2 x 2 convs on the input grid (4/9 of its flops); upsample_phases=False, or a map one pixel wide: 3 x 3 form"""
+        x, w = s[0], self.w
+        if not (self.upsample_phases and W >= 2):
+            return self.issue(ops.conv3x3, x, (B, H, W), w[k + "weight"], w[k + "bias"], B * 4 * H * W, upsample=True)
+        uc = self._oc(B * 4 * H * W, x.shape[-1], x)
+        up = torch.empty((B * 4 * H * W, x.shape[-1]), device=x.device, dtype=torch.float16)
+        for ph in range(4):
+            ops.conv3x3(x, B, H, W, w[k + f"phase.{ph}"], w[k + "bias"], phase=ph, out=up, out_carry=uc)
+        return up, uc
+
+
+class _Fp32Split:
+    """A stream is one fp32 tensor; operands are split3 fp16 [hi | lo | hi] against `ws`, weights packed [w_hi | w_hi | w_lo]."""
+    out_dtype = torch.float32
+
+    def __init__(self, w, ws, groups, device):
+        self.w, self.ws, self.groups, self.device = w, ws, groups, device
+
+    def pack(self, x_nchw, ones_channel=-1):
+        return _pack32(x_nchw, self.device, ones_channel)
+
+    def norm(self, s, B, HW, k, silu):
+        return ops.groupnorm_f32_split(s, B, HW, self.w[k + "weight"], self.w[k + "bias"], EPS, silu, groups=self.groups)
+
+    def issue(self, fn, a, geom, weight, bias, rows, resid=None, **kw):
+        return fn(a, *geom, weight, bias, resid=resid, out_f32=True, **kw)
+
+    def raw(self, s):
+        xs, inv = ops.split_cast_guarded(s)
+        return xs, {"alpha": inv}
+
+    def upsample(self, s, B, H, W, k):
+        xs, kw = self.raw(s)
+        return self.issue(ops.conv3x3, xs, (B, H, W), self.ws[k + "weight"], self.w[k + "bias"], B * 4 * H * W, upsample=True, **kw)
 
 
 class AutoencoderKL:
@@ -282,193 +362,75 @@ class AutoencoderKL:
             ops.attention_apply(pr, vt[b0:b0 + bc], bc, 1, N, C, out=o[b0 * N:(b0 + bc) * N])
         return o
 
-    # ------------------------------------------------------------------ fp32-fidelity path (dtype == torch.float32)
-    def _split_weights(self):
-        """[w_hi | w_hi | w_lo] per tap for every conv / projection whose input is a split3 tensor, from the fp32 masters."""
-        if self._ws is not None:
-            return self._ws
-        sd = {k: v.detach().to("cpu", torch.float32) for k, v in self._sd_ref.items()}
-        dev, cfg = self.device, self.cfg
-        S = {}
+    def eval(self):
+        return self
 
-        def conv(key, w=None, cin_pad=None):
-            w = sd[key] if w is None else w                                   # [O, I, kh, kw]
-            if cin_pad:
-                wp = torch.zeros(w.shape[0], cin_pad, *w.shape[2:]); wp[:, :w.shape[1]] = w; w = wp
-            o = w.shape[0]
-            S[key] = ops.split_weight(w.permute(0, 2, 3, 1)).reshape(o, -1).to(dev)          # [O, taps * 3I]
+    # ------------------------------------------------------------------ the topology, once, in the arithmetic `A` that _arithmetic picked
+    def _arithmetic(self):
+        if self.dtype != torch.float32:
+            return _Fp16Carry(self.w, self.cfg.norm_num_groups, self.carry, self.upsample_phases)
+        if self._ws is None:
+            self._ws = _split_vae_weights(_fold_state_dict(self.cfg, self._sd_ref), self.device)
+        return _Fp32Split(self.w, self._ws, self.cfg.norm_num_groups, self.device)
 
-        def dense(key, w):
-            S[key] = ops.split_weight(w.reshape(w.shape[0], -1)).to(dev)
-
-        def resnet(p):
-            conv(p + "conv1.weight"); conv(p + "conv2.weight")
-            if p + "conv_shortcut.weight" in sd:
-                conv(p + "conv_shortcut.weight")
-
-        def mid(p):
-            resnet(p + "resnets.0."); resnet(p + "resnets.1.")
-            a = p + "attentions.0."
-            dense(a + "to_qk.weight", torch.cat([sd[a + "to_q.weight"], sd[a + "to_k.weight"]]))
-            dense(a + "to_v.weight", sd[a + "to_v.weight"])
-
-        ch, L, zc = list(cfg.block_out_channels), cfg.layers_per_block, cfg.latent_channels
-        conv("encoder.conv_in.weight", cin_pad=8)
-        for i in range(len(ch)):
-            for j in range(L):
-                resnet(f"encoder.down_blocks.{i}.resnets.{j}.")
-            if i < len(ch) - 1:
-                conv(f"encoder.down_blocks.{i}.downsamplers.0.conv.weight")
-        mid("encoder.mid_block.")
-        wq, wo = sd["quant_conv.weight"].reshape(2 * zc, 2 * zc), sd["encoder.conv_out.weight"]
-        for name, rows in (("mean", wq[:zc]), ("logvar", wq[zc:])):
-            w4 = torch.zeros(4, wo.shape[1], 3, 3); w4[:zc] = torch.einsum("om,mchw->ochw", rows, wo)
-            conv(f"encoder.conv_out_{name}.weight", w=w4)
-        wpq, bpq, wi = sd["post_quant_conv.weight"].reshape(zc, zc), sd["post_quant_conv.bias"], sd["decoder.conv_in.weight"]
-        w8 = torch.zeros(wi.shape[0], 8, 3, 3)
-        w8[:, :zc] = torch.einsum("ochw,cd->odhw", wi, wpq)
-        w8[:, zc] = torch.einsum("ochw,c->ohw", wi, bpq)
-        conv("decoder.conv_in.weight", w=w8)
-        mid("decoder.mid_block.")
-        for i in range(len(ch)):
-            for j in range(L + 1):
-                resnet(f"decoder.up_blocks.{i}.resnets.{j}.")
-            if i < len(ch) - 1:
-                conv(f"decoder.up_blocks.{i}.upsamplers.0.conv.weight")
-        wo = sd["decoder.conv_out.weight"]
-        w4 = torch.zeros(4, wo.shape[1], 3, 3); w4[:cfg.out_channels] = wo
-        conv("decoder.conv_out.weight", w=w4)
-        self._ws = S
-        return S
-
-    def _pack32(self, x_nchw, ones_channel=-1):
-        """NCHW fp32 (<= 8 channels) -> split3 [B*H*W, 24] of the 8-channel token-major packing (data movement + split only)."""
-        B, Cc, H, W = x_nchw.shape
-        t = torch.zeros((B, H, W, 8), device=self.device, dtype=torch.float32)
-        t[..., :Cc] = x_nchw.to(self.device, torch.float32).permute(0, 2, 3, 1)
-        if ones_channel >= 0:
-            t[..., ones_channel] = 1.0
-        return ops.split_cast(t.reshape(B * H * W, 8), 1.0)
-
-    def _resnet32(self, p, x, B, H, W):
-        w, ws, g = self.w, self._ws, self.cfg.norm_num_groups
-        h = ops.groupnorm_f32_split(x, B, H * W, w[p + "norm1.weight"], w[p + "norm1.bias"], EPS, True, groups=g)
-        h = ops.conv3x3(h, B, H, W, ws[p + "conv1.weight"], w[p + "conv1.bias"], out_f32=True)
-        h = ops.groupnorm_f32_split(h, B, H * W, w[p + "norm2.weight"], w[p + "norm2.bias"], EPS, True, groups=g)
-        sc = x
+    def _resnet(self, A, p, s, B, H, W):
+        w, ws, n = A.w, A.ws, B * H * W
+        h = A.norm(s, B, H * W, p + "norm1.", True)
+        h = A.issue(ops.conv3x3, h, (B, H, W), ws[p + "conv1.weight"], w[p + "conv1.bias"], n)
+        h = A.norm(h, B, H * W, p + "norm2.", True)
+        sc = s
         if p + "conv_shortcut.weight" in ws:
-            xs, inv = ops.split_cast_guarded(x)
-            sc = ops.gemm(xs, ws[p + "conv_shortcut.weight"], w[p + "conv_shortcut.bias"], out_f32=True, alpha=inv)
-        return ops.conv3x3(h, B, H, W, ws[p + "conv2.weight"], w[p + "conv2.bias"], resid=sc, out_f32=True)
+            x, undo = A.raw(s)
+            sc = A.issue(ops.gemm, x, (), ws[p + "conv_shortcut.weight"], w[p + "conv_shortcut.bias"], n, **undo)
+        return A.issue(ops.conv3x3, h, (B, H, W), ws[p + "conv2.weight"], w[p + "conv2.bias"], n, resid=sc)
 
-    def _attention32(self, p, x, B, H, W):
-        w, ws, g = self.w, self._ws, self.cfg.norm_num_groups
-        C, N = x.shape[1], H * W
-        h = ops.groupnorm_f32_split(x, B, N, w[p + "group_norm.weight"], w[p + "group_norm.bias"], EPS, False, groups=g)
-        qk = ops.gemm(h, ws[p + "to_qk.weight"], w[p + "to_qk.bias"])                  # fp16: bounded (GroupNorm output x weights)
+    def _attention(self, A, p, s, B, H, W):
+        """q / k / v / P stay fp16 in both arithmetics (bounded by construction: they follow a GroupNorm and a softmax)"""
+        w, ws = A.w, A.ws
+        C, N = w[p + "to_out.weight"].shape[0], H * W
+        h = A.norm(s, B, N, p + "group_norm.", False)
+        qk = ops.gemm(h, ws[p + "to_qk.weight"], w[p + "to_qk.bias"])
         q, k = qk[:, :C], qk[:, C:]
         ld = (N + 7) // 8 * 8
         vt = ops.project_vt(h, ws[p + "to_v.weight"], B, N, ld)
         scale = C ** -0.5
         o = self._attend(q, k, vt, B, N, C, ld, scale)
-        return ops.gemm(o, w[p + "to_out.weight"], w[p + "to_out.bias"], resid=x, out_f32=True)
+        return A.issue(ops.gemm, o, (), w[p + "to_out.weight"], w[p + "to_out.bias"], B * N, resid=s)
 
-    def _mid32(self, p, x, B, H, W):
-        x = self._resnet32(p + "resnets.0.", x, B, H, W)
-        x = self._attention32(p + "attentions.0.", x, B, H, W)
-        return self._resnet32(p + "resnets.1.", x, B, H, W)
+    def _mid(self, A, p, s, B, H, W):
+        s = self._resnet(A, p + "resnets.0.", s, B, H, W)
+        s = self._attention(A, p + "attentions.0.", s, B, H, W)
+        return self._resnet(A, p + "resnets.1.", s, B, H, W)
 
-    def _decode_chunk32(self, z):
-        w, ws, cfg = self.w, self._split_weights(), self.cfg
-        B, _, H, W = z.shape
-        x = ops.conv3x3(self._pack32(z, ones_channel=cfg.latent_channels), B, H, W, ws["decoder.conv_in.weight"],
-                        w["decoder.conv_in.bias"], out_f32=True)
-        x = self._mid32("decoder.mid_block.", x, B, H, W)
-        nb = len(cfg.block_out_channels)
-        for i in range(nb):
-            for j in range(cfg.layers_per_block + 1):
-                x = self._resnet32(f"decoder.up_blocks.{i}.resnets.{j}.", x, B, H, W)
-            if i < nb - 1:
-                k = f"decoder.up_blocks.{i}.upsamplers.0.conv."
-                xs, inv = ops.split_cast_guarded(x)
-                x = ops.conv3x3(xs, B, H, W, ws[k + "weight"], w[k + "bias"], upsample=True, out_f32=True, alpha=inv)
+    def _decode_body(self, A, x, B, H, W):
+        """x: conv_in's operand, the packed latent with its ones channel (A.pack) -> image [B, 3, 8H, 8W] in A.out_dtype"""
+        w, ws, cfg = A.w, A.ws, self.cfg
+        s = A.issue(ops.conv3x3, x, (B, H, W), ws["decoder.conv_in.weight"], w["decoder.conv_in.bias"], B * H * W)
+        s = self._mid(A, "decoder.mid_block.", s, B, H, W)
+        for resnets, up, _ in cfg.levels("decoder"):
+            for p, _, _ in resnets:
+                s = self._resnet(A, p, s, B, H, W)
+            if up:
+                s = A.upsample(s, B, H, W, up)
                 H, W = 2 * H, 2 * W
-        h = ops.groupnorm_f32_split(x, B, H * W, w["decoder.conv_norm_out.weight"], w["decoder.conv_norm_out.bias"], EPS, True,
-                                    groups=cfg.norm_num_groups)
-        return ops.conv_out(h, B, H, W, ws["decoder.conv_out.weight"], w["decoder.conv_out.bias"], out_dtype=torch.float32,
-                            cout=cfg.out_channels)
+        h = A.norm(s, B, H * W, "decoder.conv_norm_out.", True)
+        return ops.conv_out(h, B, H, W, ws["decoder.conv_out.weight"], w["decoder.conv_out.bias"], out_dtype=A.out_dtype, cout=cfg.out_channels)
 
-    def _encode_chunk32(self, img):
-        B, _, H, W = img.shape
-        return self._encode_split32(self._pack32(img), B, H, W)
-
-    def _encode_split32(self, x, B, H, W):
-        """x: the split3 fp16 [B * H * W, 24] operand of conv_in (_pack32's tensor, or icd_vae_ingest_f32's)"""
-        w, ws, cfg = self.w, self._split_weights(), self.cfg
-        x = ops.conv3x3(x, B, H, W, ws["encoder.conv_in.weight"], w["encoder.conv_in.bias"], out_f32=True)
-        nb = len(cfg.block_out_channels)
-        for i in range(nb):
-            for j in range(cfg.layers_per_block):
-                x = self._resnet32(f"encoder.down_blocks.{i}.resnets.{j}.", x, B, H, W)
-            if i < nb - 1:
-                k = f"encoder.down_blocks.{i}.downsamplers.0.conv."
-                xs, inv = ops.split_cast_guarded(x)
-                x = ops.conv3x3(xs, B, H, W, ws[k + "weight"], w[k + "bias"], stride=2, pad_hi=True, out_f32=True, alpha=inv)
+    def _encode_body(self, A, x, B, H, W):
+        """x: conv_in's operand - A.pack of the image, icd_vae_ingest's tensor (fp16) or icd_vae_ingest_f32's (fp32) -> (mean, logvar)"""
+        w, ws = A.w, A.ws
+        s = A.issue(ops.conv3x3, x, (B, H, W), ws["encoder.conv_in.weight"], w["encoder.conv_in.bias"], B * H * W)
+        for resnets, down, _ in self.cfg.levels("encoder"):
+            for p, _, _ in resnets:
+                s = self._resnet(A, p, s, B, H, W)
+            if down:
+                x, undo = A.raw(s)
+                s = A.issue(ops.conv3x3, x, (B, H, W), ws[down + "weight"], w[down + "bias"], B * (H // 2) * (W // 2), stride=2, pad_hi=True, **undo)
                 H, W = H // 2, W // 2
-        x = self._mid32("encoder.mid_block.", x, B, H, W)
-        h = ops.groupnorm_f32_split(x, B, H * W, w["encoder.conv_norm_out.weight"], w["encoder.conv_norm_out.bias"], EPS, True,
-                                    groups=cfg.norm_num_groups)
-        mean = ops.conv_out(h, B, H, W, ws["encoder.conv_out_mean.weight"], w["encoder.conv_out_mean.bias"], out_dtype=torch.float32, cout=4)
-        logvar = ops.conv_out(h, B, H, W, ws["encoder.conv_out_logvar.weight"], w["encoder.conv_out_logvar.bias"], out_dtype=torch.float32,
-                              cout=4)
-        return mean, logvar
-
-    def eval(self):
-        return self
-
-    # -- blocks (token-major fp16 [B*H*W, C]).  Round 6: the residual stream carries its rounding error (`self.carry`, default on): every
-    # x <- x + f(x) of a ResnetBlock2D / the mid-block attention keeps what the fp16 rounding of the sum lost in one bf8 byte per element
-    # (icd_gemm_desc.resid_carry / out_carry, the UNet's residual mode 2) and every GroupNorm normalises fp16 + carry (icd_groupnorm_carry):
-    # the stream behaves like a 14-bit-mantissa tensor.  A stream is the pair (x, xc); xc None = no carry yet.
-    def _gn(self, x, xc, B, HW, wk, bk, silu):
-        g = self.cfg.norm_num_groups
-        if xc is None:
-            return ops.groupnorm(x, B, HW, self.w[wk], self.w[bk], EPS, silu, groups=g)
-        return ops.groupnorm_carry(x, B, HW, self.w[wk], self.w[bk], EPS, silu, carry=xc, groups=g)
-
-    def _oc(self, rows, cols, like):
-        return torch.empty((rows, cols), device=like.device, dtype=torch.uint8) if self.carry else None
-
-    def _resnet(self, p, x, xc, B, H, W):
-        w = self.w
-        h = self._gn(x, xc, B, H * W, p + "norm1.weight", p + "norm1.bias", True)
-        c1 = self._oc(h.shape[0], w[p + "conv1.weight"].shape[0], h)
-        h = ops.conv3x3(h, B, H, W, w[p + "conv1.weight"], w[p + "conv1.bias"], out_carry=c1)
-        h = self._gn(h, c1, B, H * W, p + "norm2.weight", p + "norm2.bias", True)
-        sc, scc = x, xc
-        if p + "conv_shortcut.weight" in w:
-            scc = self._oc(x.shape[0], w[p + "conv_shortcut.weight"].shape[0], x)
-            sc = ops.gemm(x, w[p + "conv_shortcut.weight"], w[p + "conv_shortcut.bias"], out_carry=scc)
-        oc = self._oc(sc.shape[0], sc.shape[1], sc)
-        return ops.conv3x3(h, B, H, W, w[p + "conv2.weight"], w[p + "conv2.bias"], resid=sc, resid_carry=scc, out_carry=oc), oc
-
-    def _attention(self, p, x, xc, B, H, W):
-        w = self.w
-        C, N = x.shape[1], H * W
-        h = self._gn(x, xc, B, N, p + "group_norm.weight", p + "group_norm.bias", False)
-        qk = ops.gemm(h, w[p + "to_qk.weight"], w[p + "to_qk.bias"])
-        q, k = qk[:, :C], qk[:, C:]
-        ld = (N + 7) // 8 * 8
-        vt = ops.project_vt(h, w[p + "to_v.weight"], B, N, ld)
-        scale = C ** -0.5
-        o = self._attend(q, k, vt, B, N, C, ld, scale)
-        oc = self._oc(x.shape[0], x.shape[1], x)
-        return ops.gemm(o, w[p + "to_out.weight"], w[p + "to_out.bias"], resid=x, resid_carry=xc, out_carry=oc), oc
-
-    def _mid(self, p, x, xc, B, H, W):
-        x, xc = self._resnet(p + "resnets.0.", x, xc, B, H, W)
-        x, xc = self._attention(p + "attentions.0.", x, xc, B, H, W)
-        return self._resnet(p + "resnets.1.", x, xc, B, H, W)
+        s = self._mid(A, "encoder.mid_block.", s, B, H, W)
+        h = A.norm(s, B, H * W, "encoder.conv_norm_out.", True)
+        return tuple(ops.conv_out(h, B, H, W, ws[f"encoder.conv_out_{n}.weight"], w[f"encoder.conv_out_{n}.bias"], out_dtype=A.out_dtype, cout=4)
+                     for n in ("mean", "logvar"))
 
     # -- public
     @torch.no_grad()
@@ -479,37 +441,13 @@ class AutoencoderKL:
         z = z.to(self.device)
         if z.dtype not in (torch.float16, torch.float32):
             z = z.float()
-        chunk = self._decode_chunk32 if self.dtype == torch.float32 else self._decode_chunk
-        outs = [chunk(z[i:i + self.max_chunk].contiguous()) for i in range(0, z.shape[0], self.max_chunk)]
+        A, (H, W) = self._arithmetic(), z.shape[2:]
+        outs = []
+        for i in range(0, z.shape[0], self.max_chunk):
+            c = z[i:i + self.max_chunk].contiguous()
+            outs.append(self._decode_body(A, A.pack(c, ones_channel=self.cfg.latent_channels), c.shape[0], H, W))
         img = (outs[0] if len(outs) == 1 else torch.cat(outs)).to(self.dtype)
         return _Out(sample=img) if return_dict else (img,)
-
-    def _decode_chunk(self, z):
-        w, cfg = self.w, self.cfg
-        B, _, H, W = z.shape
-        x = ops.pack_nchw(z, ones_channel=cfg.latent_channels)
-        xc = self._oc(B * H * W, w["decoder.conv_in.weight"].shape[0], x)
-        x = ops.conv3x3(x, B, H, W, w["decoder.conv_in.weight"], w["decoder.conv_in.bias"], out_carry=xc)
-        x, xc = self._mid("decoder.mid_block.", x, xc, B, H, W)
-        nb = len(cfg.block_out_channels)
-        for i in range(nb):
-            for j in range(cfg.layers_per_block + 1):
-                x, xc = self._resnet(f"decoder.up_blocks.{i}.resnets.{j}.", x, xc, B, H, W)
-            if i < nb - 1:
-                k = f"decoder.up_blocks.{i}.upsamplers.0.conv."
-                uc = self._oc(B * 4 * H * W, x.shape[-1], x)
-                if self.upsample_phases and W >= 2:
-                    up = torch.empty((B * 4 * H * W, x.shape[-1]), device=x.device, dtype=torch.float16)
-                    for ph in range(4):
-                        ops.conv3x3(x, B, H, W, w[k + f"phase.{ph}"], w[k + "bias"], phase=ph, out=up, out_carry=uc)
-                    x = up
-                else:
-                    x = ops.conv3x3(x, B, H, W, w[k + "weight"], w[k + "bias"], upsample=True, out_carry=uc)
-                xc = uc
-                H, W = 2 * H, 2 * W
-        x = self._gn(x, xc, B, H * W, "decoder.conv_norm_out.weight", "decoder.conv_norm_out.bias", True)
-        return ops.conv_out(x, B, H, W, w["decoder.conv_out.weight"], w["decoder.conv_out.bias"],
-                            out_dtype=torch.float32 if self.dtype == torch.float32 else torch.float16, cout=cfg.out_channels)
 
     @torch.no_grad()
     def encode(self, x, return_dict=True):
@@ -519,8 +457,11 @@ class AutoencoderKL:
         x = x.to(self.device)
         if x.dtype not in (torch.float16, torch.float32):
             x = x.float()
-        chunk = self._encode_chunk32 if self.dtype == torch.float32 else self._encode_chunk
-        outs = [chunk(x[i:i + self.max_chunk].contiguous()) for i in range(0, x.shape[0], self.max_chunk)]
+        A, (H, W) = self._arithmetic(), x.shape[2:]
+        outs = []
+        for i in range(0, x.shape[0], self.max_chunk):
+            c = x[i:i + self.max_chunk].contiguous()
+            outs.append(self._encode_body(A, A.pack(c), c.shape[0], H, W))
         mean = torch.cat([o[0] for o in outs]).to(self.dtype)
         logvar = torch.cat([o[1] for o in outs]).to(self.dtype)
         dist = LatentDist(mean, logvar)
@@ -532,7 +473,7 @@ class AutoencoderKL:
         whose sizes may differ, resized like np.array(PIL.Image.resize((size, size))) (size=None: their own, common, square size) ->
         latent_dist, the bits `encode` gives the host route's `torch.from_numpy(arr).float() / 127.5 - 1` of the resized arrays.
         fp16: icd_vae_ingest writes conv_in's input.  fp32 fidelity: the resized bytes go through the host route's own fp32 values (a
-        256-entry table evaluated by that very expression on the host) into _encode_chunk32.  The images are ingested size by size and
+        256-entry table evaluated by that very expression on the host) and _pack32.  The images are ingested size by size and
         encoded in the caller's order, max_chunk at a time like `encode`.  want_bytes: the result also carries the resized bytes as
         ['images'], uint8 [B, size, size, 3].
         rule='image_processor' (fp32 fidelity only; the SDXL route): the same resize, then diffusers' VaeImageProcessor.preprocess,
@@ -583,44 +524,17 @@ class AutoencoderKL:
         one = len(groups) == 1
         x8 = x8[0] if one else torch.cat([x8[i] for i in range(len(groups))])
         u8 = None if u8[0] is None else (u8[0] if one else torch.cat([u8[i] for i in range(len(groups))]))
-        B, outs = x8.shape[0] // (size * size), []
+        B, outs, A = x8.shape[0] // (size * size), [], self._arithmetic()
         if f32 and not processor:
             lut = (torch.arange(256, dtype=torch.uint8).float() / 127.5 - 1).to(self.device)          # the host route's values, exactly
         for i in range(0, B, self.max_chunk):
             n = min(self.max_chunk, B - i)
-            if processor:
-                outs.append(self._encode_split32(x8[i * size * size:(i + n) * size * size], n, size, size))
-            elif f32:
-                outs.append(self._encode_chunk32(lut[u8[i:i + n].long()].permute(0, 3, 1, 2).contiguous()))
-            else:
-                outs.append(self._encode_packed(x8[i * size * size:(i + n) * size * size], n, size, size))
+            if f32 and not processor:
+                first = A.pack(lut[u8[i:i + n].long()].permute(0, 3, 1, 2).contiguous())
+            else:                                                # the ingest kernel wrote this arithmetic's operand
+                first = x8[i * size * size:(i + n) * size * size]
+            outs.append(self._encode_body(A, first, n, size, size))
         dist = LatentDist(torch.cat([o[0] for o in outs]).to(self.dtype), torch.cat([o[1] for o in outs]).to(self.dtype))
         if not return_dict:
             return (dist,)
         return _Out(latent_dist=dist, images=u8) if want_bytes else _Out(latent_dist=dist)
-
-    def _encode_chunk(self, img):
-        B, _, H, W = img.shape
-        return self._encode_packed(ops.pack_nchw(img), B, H, W)
-
-    def _encode_packed(self, x, B, H, W):
-        """x: the token-major fp16 [B * H * W, 8] input of conv_in (channels past the image's zero)"""
-        w, cfg = self.w, self.cfg
-        xc = self._oc(B * H * W, w["encoder.conv_in.weight"].shape[0], x)
-        x = ops.conv3x3(x, B, H, W, w["encoder.conv_in.weight"], w["encoder.conv_in.bias"], out_carry=xc)
-        nb = len(cfg.block_out_channels)
-        for i in range(nb):
-            for j in range(cfg.layers_per_block):
-                x, xc = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}.", x, xc, B, H, W)
-            if i < nb - 1:
-                k = f"encoder.down_blocks.{i}.downsamplers.0.conv."
-                dc = self._oc(B * (H // 2) * (W // 2), x.shape[-1], x)
-                x = ops.conv3x3(x, B, H, W, w[k + "weight"], w[k + "bias"], stride=2, pad_hi=True, out_carry=dc)
-                xc = dc
-                H, W = H // 2, W // 2
-        x, xc = self._mid("encoder.mid_block.", x, xc, B, H, W)
-        x = self._gn(x, xc, B, H * W, "encoder.conv_norm_out.weight", "encoder.conv_norm_out.bias", True)
-        od = torch.float32 if self.dtype == torch.float32 else torch.float16
-        mean = ops.conv_out(x, B, H, W, w["encoder.conv_out_mean.weight"], w["encoder.conv_out_mean.bias"], out_dtype=od, cout=4)
-        logvar = ops.conv_out(x, B, H, W, w["encoder.conv_out_logvar.weight"], w["encoder.conv_out_logvar.bias"], out_dtype=od, cout=4)
-        return mean, logvar

@@ -1,12 +1,11 @@
 """SDXL edits on the device: uint8 images into the fp32-fidelity VAE encoder (icd_vae_ingest_f32) and uint8 images out of the sampler
-(icd_image_to_u8_round), against the host route - Pillow's resize, pipelines._ImageProcessor (diffusers' VaeImageProcessor), AutoencoderKL
-._pack32 - and its numpy restatement (tests/sdxl_images_ref.py).
+(icd_image_to_u8_round), against the host route - Pillow's resize, pipelines._ImageProcessor (diffusers' VaeImageProcessor), vae._pack32
+- and its numpy restatement (tests/sdxl_images_ref.py).
 
 Bars.  Every comparison is for equality: the resample is integer arithmetic, the ingest value is a division, a doubling and a subtraction
 in fp32 followed by the split's two roundings, the output kernel makes torch's and numpy's roundings one by one, and the encoder sees the
 same operand bits on both routes."""
 import ctypes
-import types
 
 import numpy as np
 import pytest
@@ -42,13 +41,13 @@ def _ingest_cabi(dev, S, want_bytes):
 
 
 def _host_operand(resized_u8):
-    """Pillow's bytes -> _ImageProcessor.preprocess -> AutoencoderKL._pack32: the first operand of the fp32-fidelity encoder, host route"""
+    """Pillow's bytes -> _ImageProcessor.preprocess -> vae._pack32: the first operand of the fp32-fidelity encoder, host route"""
     from PIL import Image
     from invertible_cd_amd import vae
     from invertible_cd_amd.pipelines import _ImageProcessor
     x = _ImageProcessor().preprocess([Image.fromarray(a) for a in resized_u8])
     assert x.dtype == torch.float32 and tuple(x.shape) == (resized_u8.shape[0], 3) + resized_u8.shape[1:3]
-    return vae.AutoencoderKL._pack32(types.SimpleNamespace(device=torch.device("cuda")), x)
+    return vae._pack32(x, torch.device("cuda"))
 
 
 def _all_values_image():

@@ -4,7 +4,7 @@
     python tools/sdxl_device_images_bench.py [--n 8] [--size 1024] [--reps 20] [--warmup 3]
 
 In: n images of size x size (seeded noise) -> the first operand of the fp32-fidelity encoder, split3 fp16 [n * size^2, 24].  Host route:
-_ImageProcessor.preprocess of the PIL images, the cast to fp16 and upload, the upcast, AutoencoderKL._pack32 (prepare_latents in front of
+_ImageProcessor.preprocess of the PIL images, the cast to fp16 and upload, the upcast, vae._pack32 (prepare_latents in front of
 the encoder).  Device route: the uint8 batch already on the device -> icd_vae_ingest_f32 and the zero fill of the lo half that an fp16
 pipeline asks for (encode_images(rule='image_processor', image_dtype=float16)); also shown with the upload of the bytes in front.
 Out: a decoded fp32 sample [n, 3, size, size] on the device -> _ImageProcessor.postprocess(..., 'pil') (copy to the host, numpy, PIL)
@@ -16,7 +16,6 @@ import os
 import statistics
 import sys
 import time
-import types
 
 import numpy as np
 import torch
@@ -49,7 +48,6 @@ def main():
     from invertible_cd_amd.pipelines import _ImageProcessor
     n, S, reps, warmup = args.n, args.size, args.reps, args.warmup
     ip = _ImageProcessor()
-    me = types.SimpleNamespace(device=torch.device("cuda"))
     print(f"# {torch.cuda.get_device_name(0)}, kernel sources {_lib.build_sha()}, n = {n}, {S} x {S}, {reps} timed repetitions after "
           f"{warmup} warm-up repetitions, wall time around a synchronise")
     arr = np.random.default_rng(0).integers(0, 256, (n, S, S, 3), dtype=np.uint8)
@@ -59,7 +57,7 @@ def main():
 
     def host_in():
         x = ip.preprocess(pils).to(device="cuda", dtype=torch.float16)
-        return vae.AutoencoderKL._pack32(me, x.float())
+        return vae._pack32(x.float(), torch.device("cuda"))
 
     def dev_in(u8=dev_u8):
         a, _ = ops.vae_ingest_f32(u8, S)
