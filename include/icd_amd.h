@@ -370,7 +370,8 @@ int icd_attention_plan(const icd_attention_query* q, icd_attention_info* out);
 
 /* Sinusoidal embeddings.  kind 0: diffusers Timesteps(dim, flip_sin_to_cos=True, shift=0) -> [cos || sin];
  * kind 1: guidance_scale_embedding (utils/generation.py:96-122) -> [sin || cos] of 1000*w, denominator half-1.
- * vals: fp32 [n] on device; out fp16 [n, dim]. */
+ * vals: fp32 [n] on device; out fp16 [n, dim].  kind 0: dim even, >= 2.  kind 1: dim >= 4 (at dim 2 and 3 the frequency step would
+ * divide by half - 1 = 0: refused); an odd dim leaves a last column of zeros. */
 int icd_sinusoid(const float* vals, int32_t n, int32_t dim, int32_t kind, void* out, void* stream);
 /* The same with fp32 output and the correctly rounded fp32 frequency table (the precise time-embedding path, ICD_SPLIT_TEMB). */
 int icd_sinusoid_f32(const float* vals, int32_t n, int32_t dim, int32_t kind, float* out, void* stream);

@@ -294,6 +294,7 @@ extern "C" int icd_sinusoid(const float* vals, int32_t n, int32_t dim, int32_t k
     ICD_CHECK_ARG(vals && out && n > 0 && dim >= 2, "icd_sinusoid: bad arguments");
     ICD_CHECK_ARG(kind == 0 || kind == 1, "icd_sinusoid: kind must be 0 or 1");
     ICD_CHECK_ARG(kind == 1 || dim % 2 == 0, "icd_sinusoid: Timesteps dim must be even");
+    ICD_CHECK_ARG(kind == 0 || dim >= 4, "icd_sinusoid: the guidance embedding needs dim >= 4: its frequency step divides by dim / 2 - 1 (got %d)", dim);
     const int total = n * (dim / 2);
     hipLaunchKernelGGL(sinusoid_kernel<half_t>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, vals, n, dim, kind,
                        (half_t*)out);
@@ -305,6 +306,7 @@ extern "C" int icd_sinusoid_f32(const float* vals, int32_t n, int32_t dim, int32
     ICD_CHECK_ARG(vals && out && n > 0 && dim >= 2, "icd_sinusoid_f32: bad arguments");
     ICD_CHECK_ARG(kind == 0 || kind == 1, "icd_sinusoid_f32: kind must be 0 or 1");
     ICD_CHECK_ARG(kind == 1 || dim % 2 == 0, "icd_sinusoid_f32: Timesteps dim must be even");
+    ICD_CHECK_ARG(kind == 0 || dim >= 4, "icd_sinusoid_f32: the guidance embedding needs dim >= 4: its frequency step divides by dim / 2 - 1 (got %d)", dim);
     const int total = n * (dim / 2);
     hipLaunchKernelGGL(sinusoid_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, vals, n, dim, kind, out);
     ICD_CHECK_LAUNCH("icd_sinusoid_f32");
