@@ -13,13 +13,14 @@ What is different underneath (MI355X-first):
     only - identical outputs, half the FLOPs; controllers still see exactly the rows their `forward` saw before;
   * per-step device constants (w-embedding, timestep, boundary coefficients) are cached on the GPU, so the 4-step loop
     issues no host->device copies and never synchronises (the reference syncs at t.item() every step).
+Everything the loops share with the SDXL sampler (the numeric helpers, the endpoint rule, the constant cache, the boundary step) is
+sampling.py's.
 """
-from typing import Union
-
 import numpy as np
 import torch
 
-from . import p2p
+from . import p2p, sampling
+from .sampling import extract_into_tensor, guidance_scale_embedding, linear_schedule_old, predicted_origin  # noqa: F401  (drop-in names)
 
 
 # ----------------------------------------------------------------------------------------------------------- runner
@@ -33,7 +34,7 @@ def runner(model, prompt, controller, solver, is_cons_forward=False, num_inferen
     p2p.ControllerBatch of G members and `latent` [G, 4, 64, 64] (or None: G draws from `generator` in one call).  Each group's
     latent is repeated P times (init_latent per group), per-step `uncond_embeddings` [G, 77, 768] are repeated per group, and the
     G * P outputs come back group-major, each group as a run of its own would give it.  Returns (images | latents, [G, 4, 64, 64])."""
-    groups = _prompt_groups(prompt, controller)
+    groups = sampling.prompt_groups(prompt, controller)
     p2p.register_attention_control(model, controller)
     if groups is None:
         solver.init_prompt(prompt, None)
@@ -67,38 +68,7 @@ def runner(model, prompt, controller, solver, is_cons_forward=False, num_inferen
     return image, latent
 
 
-def _prompt_groups(prompt, controller):
-    """(G, P) for a list of G lists of P prompts (batched editing), None for the reference's flat list."""
-    if isinstance(prompt, str) or not any(isinstance(p, (list, tuple)) for p in prompt):
-        return None
-    if not all(isinstance(p, (list, tuple)) and len(p) > 0 for p in prompt):
-        raise ValueError("runner: a prompt list mixes groups (lists) and single prompts")
-    sizes = {len(p) for p in prompt}
-    if len(sizes) != 1:
-        raise ValueError(f"runner: every prompt group must have the same size (got {sorted(sizes)}); split the batch by size")
-    G, P = len(prompt), sizes.pop()
-    if controller is not None:
-        if not isinstance(controller, p2p.ControllerBatch):
-            raise ValueError("runner: grouped prompts need a p2p.ControllerBatch (one controller per group)")
-        if controller.n_groups != G or (controller.is_edit and controller.n_prompts != P):
-            raise ValueError(f"runner: {G} groups of {P} prompts do not match the ControllerBatch "
-                             f"({controller.n_groups} members of {controller.n_prompts} prompts)")
-    return G, P
-
-
 # ----------------------------------------------------------------------------------------------------------- schedules
-def linear_schedule_old(t, guidance_scale, tau1, tau2):
-    """gamma(t/1000) * gs with gamma = 1 below tau1, 0 above tau2, linear in between (utils/generation.py:74-82)."""
-    u = t / 1000
-    if u <= tau1:
-        gamma = 1.0
-    elif u >= tau2:
-        gamma = 0.0
-    else:
-        gamma = (tau2 - u) / (tau2 - tau1)
-    return gamma * guidance_scale
-
-
 def linear_schedule(t, guidance_scale, tau1=0.4, tau2=0.8):
     """Classic-CFG variant: gs below tau1, 1.0 above tau2 (utils/generation.py:85-93)."""
     u = t / 1000
@@ -109,69 +79,12 @@ def linear_schedule(t, guidance_scale, tau1=0.4, tau2=0.8):
     return (tau2 - u) / (tau2 - tau1) * (guidance_scale - 1.0) + 1.0
 
 
-def guidance_scale_embedding(w, embedding_dim=512, dtype=torch.float32):
-    """[sin(1000 w f) || cos(1000 w f)], f_i = exp(-ln(1e4) i / (half - 1))  (utils/generation.py:96-122)."""
-    assert len(w.shape) == 1
-    w = w * 1000.0
-    half_dim = embedding_dim // 2
-    step = torch.log(torch.tensor(10000.0)) / (half_dim - 1)
-    freqs = torch.exp(torch.arange(half_dim, dtype=dtype) * -step)
-    ang = w.to(dtype)[:, None] * freqs[None, :]
-    emb = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1)
-    if embedding_dim % 2 == 1:
-        emb = torch.nn.functional.pad(emb, (0, 1))
-    assert emb.shape == (w.shape[0], embedding_dim)
-    return emb
-
-
-# ----------------------------------------------------------------------------------------------------------- boundary step
-def extract_into_tensor(a, t, x_shape):
-    b, *_ = t.shape
-    return a.gather(-1, t).reshape(b, *((1,) * (len(x_shape) - 1)))
-
-
-def predicted_origin(model_output, timesteps, boundary_timesteps, sample, prediction_type, alphas, sigmas):
-    """x0-prediction followed by the jump to the boundary timestep s (utils/generation.py:136-155).
-
-    Generic torch expression (any device); the sampler loops below use the fused HIP kernel icd_x0_step, which is
-    bit-identical to this expression evaluated in fp32."""
-    sigmas_s = extract_into_tensor(sigmas, boundary_timesteps, sample.shape)
-    alphas_s = extract_into_tensor(alphas, boundary_timesteps, sample.shape)
-    sigmas_t = extract_into_tensor(sigmas, timesteps, sample.shape)
-    alphas_t = extract_into_tensor(alphas, timesteps, sample.shape)
-    alphas_s[boundary_timesteps == 0] = 1.0          # hard boundary at s = 0
-    sigmas_s[boundary_timesteps == 0] = 0.0
-    if prediction_type == "epsilon":
-        x0 = (sample - sigmas_t * model_output) / alphas_t
-        return alphas_s * x0 + sigmas_s * model_output
-    if prediction_type == "v_prediction":
-        assert boundary_timesteps == 0, "v_prediction does not support multiple endpoints at the moment"
-        return alphas_t * sample - sigmas_t * model_output
-    raise ValueError(f"Prediction type {prediction_type} currently not supported.")
-
-
 def guided_step(noise_prediction_text, noise_pred_uncond, t, guidance_scale, dynamic_guidance=False, tau1=0.4, tau2=0.6):
     if dynamic_guidance:
         if not isinstance(t, int):
             t = t.item()
         guidance_scale = linear_schedule(t, guidance_scale, tau1=tau1, tau2=tau2)
     return noise_pred_uncond + guidance_scale * (noise_prediction_text - noise_pred_uncond)
-
-
-class _editing:
-    """`with unet.editing():` when `on` and the model's UNet is the native one (anything else: no-op)."""
-
-    def __init__(self, model, on):
-        ctx = getattr(getattr(model, "unet", None), "editing", None)
-        self._ctx = ctx() if (on and ctx is not None) else None
-
-    def __enter__(self):
-        if self._ctx is not None:
-            self._ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self._ctx is not None:
-            self._ctx.__exit__(*exc)
 
 
 # ----------------------------------------------------------------------------------------------------------- Generator
@@ -193,10 +106,9 @@ class Generator:
         self.model.scheduler.set_timesteps(n_steps)
         self.prompt = None
         self.context = None
-        self.ddim_timesteps = torch.from_numpy(
-            (np.arange(1, n_steps + 1) * (1000 // n_steps)).round().astype(np.int64) - 1).long()
+        self.ddim_timesteps = torch.from_numpy(sampling.ddim_grid(n_steps)).long()
         self.start_timestep = start_timestep
-        self._dev_cache = {}
+        self._consts = sampling.ConstCache()     # per Generator: the schedules of its models
 
         if reverse_timesteps is None or forward_timesteps is None:
             ends, inv_ends = self._create_forward_inverse_timesteps(num_endpoints, n_steps, max_forward_timestep_index)
@@ -217,11 +129,8 @@ class Generator:
         print(f"Endpoints forward CTM: {self.forward_timesteps}, {self.forward_boundary_timesteps}")
 
     def _create_forward_inverse_timesteps(self, num_endpoints, n_steps, max_inverse_timestep_index):
-        interval = n_steps // num_endpoints + int(n_steps % num_endpoints > 0)
-        idx = torch.arange(interval, n_steps, interval) - 1
-        inv_idx = torch.tensor(idx.tolist() + [max_inverse_timestep_index])
-        endpoints = torch.tensor([0] + self.ddim_timesteps[idx].tolist())
-        return endpoints, self.ddim_timesteps[inv_idx]
+        assert n_steps == len(self.ddim_timesteps)
+        return sampling.interval_endpoints(self.ddim_timesteps, num_endpoints, max_inverse_timestep_index)
 
     @property
     def scheduler(self):
@@ -262,14 +171,6 @@ class Generator:
             return (0.0, 0.0, 0.0, float(guidance_scale))
         return (float(guidance_scale),) * n_doubled
 
-    def _cached(self, key, make):
-        v = self._dev_cache.get(key)
-        if v is None:
-            if len(self._dev_cache) > 256:
-                self._dev_cache.clear()
-            v = self._dev_cache[key] = make()
-        return v
-
     def _can_skip_uncond(self, model):
         unet = model.unet
         if not (self.eliminate_dead_uncond and hasattr(unet, "attn_cond_only")):
@@ -287,19 +188,14 @@ class Generator:
             if dynamic_guidance:
                 t_item = t if isinstance(t, int) else t.item()
                 guidance_scale = linear_schedule_old(t_item, guidance_scale, tau1=tau1, tau2=tau2)
-            wv = self._w_vector(2 * B, guidance_scale)
-            w_embedding = self._cached(("w", wv, w_embed_dim, str(latent.device), latent.dtype), lambda: guidance_scale_embedding(
-                torch.tensor(wv), embedding_dim=w_embed_dim).to(device=latent.device, dtype=latent.dtype))
+            w_embedding = sampling.w_embedding(self._w_vector(2 * B, guidance_scale), w_embed_dim, latent.device, latent.dtype,
+                                               self._consts)
         unet = model.unet
         if w_embedding is not None and self._can_skip_uncond(model):
             # the unconditional half is dead code on this branch (only `noise_prediction_text` is returned): skip it
-            unet.attn_cond_only = True
-            try:
-                out = unet(latent.to(dtype=unet.dtype), t, timestep_cond=w_embedding[B:].to(dtype=unet.dtype),
-                           encoder_hidden_states=context[B:])["sample"]
-            finally:
-                unet.attn_cond_only = False
-            return out
+            with sampling.cond_only(unet):
+                return unet(latent.to(dtype=unet.dtype), t, timestep_cond=w_embedding[B:].to(dtype=unet.dtype),
+                            encoder_hidden_states=context[B:])["sample"]
         latents_input = torch.cat([latent] * 2)
         noise_pred = unet(latents_input.to(dtype=unet.dtype), t,
                           timestep_cond=w_embedding.to(dtype=unet.dtype) if w_embed_dim > 0 else None,
@@ -316,9 +212,7 @@ class Generator:
         latents = 1 / 0.18215 * latents.detach()
         image = self.model.vae.decode(latents.to(dtype=self.model.dtype))['sample']
         if return_type == 'np':
-            image = (image / 2 + 0.5).clamp(0, 1)
-            image = image.cpu().permute(0, 2, 3, 1).numpy()[0]
-            image = (image * 255).astype(np.uint8)
+            image = _to_uint8_host(image[:1])[0]
         elif return_type == 'uint8_device':
             image = _to_uint8_device(image)
         return image
@@ -364,7 +258,7 @@ class Generator:
         all_latent = [latent]
         latent = latent.clone().detach()
         ts = self.model.scheduler.timesteps
-        with _editing(self.model, is_forward or dynamic_guidance):
+        with sampling.editing(self.model, is_forward or dynamic_guidance):
             for i in range(n_steps):
                 if uncond_embeddings is not None:
                     self.init_prompt(self.prompt, uncond_embeddings[i])
@@ -394,27 +288,10 @@ class Generator:
 
     # ------------------------------------------------------------------ consistency loops (THE hot path)
     def _boundary_step(self, noise_pred, t, s, latent, alpha_schedule, sigma_schedule):
-        """predicted_origin for a whole batch at one (t, s) pair - fused HIP kernel on the GPU."""
-        ptype = self.model.scheduler.config.prediction_type
-        B = len(latent)
-        if latent.is_cuda and ptype == "epsilon":
-            from . import ops
-            ti, si = int(t), int(s)
-
-            def make():
-                a_s, s_s = (1.0, 0.0) if si == 0 else (float(alpha_schedule[si]), float(sigma_schedule[si]))
-                row = [float(alpha_schedule[ti]), float(sigma_schedule[ti]), a_s, s_s]
-                return torch.tensor([row] * B, dtype=torch.float32).to(latent.device)
-            coef = self._cached(("coef", ti, si, B, str(latent.device)), make)
-            out_dtype = torch.promote_types(torch.promote_types(latent.dtype, noise_pred.dtype), torch.float32)
-            return ops.x0_step(latent.contiguous(), noise_pred.contiguous(), coef, out_dtype=out_dtype)
-        dev = latent.device
-        return predicted_origin(noise_pred, torch.tensor([t] * B, device=dev), torch.tensor([s] * B, device=dev), latent,
-                                ptype, alpha_schedule.to(dev), sigma_schedule.to(dev))
-
-    def _schedules(self):
-        ac = self.model.scheduler.alphas_cumprod
-        return torch.sqrt(ac).cpu(), torch.sqrt(1 - ac).cpu()
+        """sampling.boundary_step with the fp32 latent chain of the reference: the dtype predicted_origin gives on fp32 tables."""
+        out_dtype = torch.promote_types(torch.promote_types(latent.dtype, noise_pred.dtype), torch.float32)
+        return sampling.boundary_step(noise_pred, t, s, latent, self.model.scheduler.config.prediction_type, alpha_schedule,
+                                      sigma_schedule, out_dtype, self._consts)
 
     @torch.no_grad()
     def cons_generation(self, latent, guidance_scale=1, dynamic_guidance=False, tau1=0.4, tau2=0.6, w_embed_dim=0,
@@ -422,10 +299,10 @@ class Generator:
         """Reverse (noise -> data) consistency sampling: one UNet call + one boundary step per (t, s) pair."""
         all_latent = [latent]
         latent = latent.clone().detach()
-        alpha_schedule, sigma_schedule = self._schedules()
+        alpha_schedule, sigma_schedule = sampling.schedules(self.model.scheduler)
         # dynamic guidance is the reference's editing schedule (utils/generation.py:74-82): such passes run at the accurate precision
         # level of the native UNet, like the inversion loop and every pass with a controller attached (unet.py: precision policy)
-        with _editing(self.reverse_cons_model, dynamic_guidance):
+        with sampling.editing(self.reverse_cons_model, dynamic_guidance):
             for t, s in zip(self.reverse_timesteps, self.reverse_boundary_timesteps):
                 noise_pred = self.get_noise_pred(model=self.reverse_cons_model, latent=latent, t=t, context=None, tau1=tau1,
                                                  tau2=tau2, w_embed_dim=w_embed_dim, guidance_scale=guidance_scale,
@@ -446,7 +323,7 @@ class Generator:
         `seed` may be a list with one seed per image (batched editing): image g is noised with
         randn((1, ...), generator=manual_seed(seed[g])) and every row is what an inversion of that image alone with seed[g] gives.
         An int keeps the one batch-wide draw."""
-        alpha_schedule, sigma_schedule = self._schedules()
+        alpha_schedule, sigma_schedule = sampling.schedules(self.model.scheduler)
         latent, image_gt = self.image2latent(image, return_bytes=True) if device_images else (self.image2latent(image), None)
         groups = None
         if isinstance(seed, (list, tuple)):
@@ -461,7 +338,7 @@ class Generator:
         image_rec = (image_gt, self.latent2image(latent, return_type='uint8_device')) if device_images else self.latent2image(latent)
         prev_groups, self.prompt_groups = self.prompt_groups, groups
         try:
-            with _editing(self.forward_cons_model, True):    # forward steps amplify the per-evaluation error: accurate precision level
+            with sampling.editing(self.forward_cons_model, True):    # forward steps amplify the per-evaluation error: accurate precision level
                 for t, s in zip(self.forward_timesteps, self.forward_boundary_timesteps):
                     noise_pred = self.get_noise_pred(model=self.forward_cons_model, latent=latent, t=t, context=None,
                                                      guidance_scale=guidance_scale, w_embed_dim=w_embed_dim, dynamic_guidance=False)
@@ -482,6 +359,13 @@ def _to_uint8_device(image):
     return (image.permute(0, 2, 3, 1) * 255).to(torch.uint8).contiguous()
 
 
+def _to_uint8_host(image):
+    """decoded NCHW sample -> uint8 NHWC numpy array, the reference's conversion (utils/generation.py)"""
+    image = (image / 2 + 0.5).clamp(0, 1)
+    image = image.cpu().permute(0, 2, 3, 1).numpy()
+    return (image * 255).astype(np.uint8)
+
+
 def _is_device_images(image):
     """uint8 NHWC images on the device: a [B, H, W, 3] tensor or a list of [H, W, 3] tensors"""
     if type(image) is torch.Tensor:
@@ -493,11 +377,7 @@ def _is_device_images(image):
 def latent2image(vae, latents, on_device=False):
     """uint8 NHWC images: a numpy array, or with on_device=True a tensor that stays on the device."""
     image = vae.decode(1 / 0.18215 * latents)['sample']
-    if on_device:
-        return _to_uint8_device(image)
-    image = (image / 2 + 0.5).clamp(0, 1)
-    image = image.cpu().permute(0, 2, 3, 1).numpy()
-    return (image * 255).astype(np.uint8)
+    return _to_uint8_device(image) if on_device else _to_uint8_host(image)
 
 
 def init_latent(latent, model, height, width, generator, batch_size):

@@ -9,13 +9,17 @@ per-step device constants are cached so the loop never synchronises.  Two delibe
 controller=)` runs the p2p controllers of the SD1.5 path on the SDXL batch (the reference's SDXL scripts register none), and
 with `use_dynamic_guidance=True` the reference only works for a batch of one (it builds
 `torch.tensor([tensor_of_len_B] * B)`, utils/generation_sdxl.py:439-440, which raises for B > 1); here the same scalar
-rule is applied to every sample, which is what the reference computes for B == 1.
+rule is applied to every sample, which is what the reference computes for B == 1.  What the loops share with the SD1.5 sampler
+(the numeric helpers, the endpoint rule, the constant cache, the boundary step) is sampling.py's.
 """
 import copy
 import random
 
 import numpy as np
 import torch
+
+from . import p2p, sampling
+from .sampling import extract_into_tensor, guidance_scale_embedding, linear_schedule_old, predicted_origin  # noqa: F401  (drop-in names)
 
 
 def encode_prompt(prompt_batch, text_encoders, tokenizers, proportion_empty_prompts, is_train=True):
@@ -52,67 +56,23 @@ def compute_embeddings(prompt_batch, original_sizes, crop_coords, proportion_emp
     return {"prompt_embeds": prompt_embeds.to(device), "text_embeds": pooled.to(device), "time_ids": time_ids}
 
 
-def extract_into_tensor(a, t, x_shape):
-    b, *_ = t.shape
-    return a.gather(-1, t).reshape(b, *((1,) * (len(x_shape) - 1)))
-
-
-def guidance_scale_embedding(w, embedding_dim=512, dtype=torch.float32):
-    """Same embedding as the SD1.5 path (utils/generation_sdxl.py:84-110)."""
-    assert len(w.shape) == 1
-    w = w * 1000.0
-    half_dim = embedding_dim // 2
-    step = torch.log(torch.tensor(10000.0)) / (half_dim - 1)
-    freqs = torch.exp(torch.arange(half_dim, dtype=dtype) * -step)
-    ang = w.to(dtype)[:, None] * freqs[None, :]
-    emb = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1)
-    if embedding_dim % 2 == 1:
-        emb = torch.nn.functional.pad(emb, (0, 1))
-    assert emb.shape == (w.shape[0], embedding_dim)
-    return emb
-
-
-def predicted_origin(model_output, timesteps, boundary_timesteps, sample, prediction_type, alphas, sigmas):
-    """utils/generation_sdxl.py:112-132 (generic torch form; the loops below use the fused HIP kernel on the GPU)."""
-    sigmas_s = extract_into_tensor(sigmas, boundary_timesteps, sample.shape)
-    alphas_s = extract_into_tensor(alphas, boundary_timesteps, sample.shape)
-    sigmas_t = extract_into_tensor(sigmas, timesteps, sample.shape)
-    alphas_t = extract_into_tensor(alphas, timesteps, sample.shape)
-    alphas_s[boundary_timesteps == 0] = 1.0
-    sigmas_s[boundary_timesteps == 0] = 0.0
-    if prediction_type == "epsilon":
-        x0 = (sample - sigmas_t * model_output) / alphas_t
-        return alphas_s * x0 + sigmas_s * model_output
-    if prediction_type == "v_prediction":
-        assert boundary_timesteps == 0, "v_prediction does not support multiple endpoints at the moment"
-        return alphas_t * sample - sigmas_t * model_output
-    raise ValueError(f"Prediction type {prediction_type} currently not supported.")
-
-
 class DDIMSolver:
     """Endpoint tables of the multi-boundary consistency model (utils/generation_sdxl.py:135-199)."""
 
     def __init__(self, alpha_cumprods, timesteps=1000, ddim_timesteps=50, num_endpoints=1, num_inverse_endpoints=1,
                  max_inverse_timestep_index=49, endpoints=None, inverse_endpoints=None):
-        ratio = timesteps // ddim_timesteps
-        grid = (np.arange(1, ddim_timesteps + 1) * ratio).round().astype(np.int64) - 1
+        grid = sampling.ddim_grid(ddim_timesteps, timesteps)
         self.ddim_timesteps = torch.from_numpy(grid).long()
         self.ddim_alpha_cumprods = torch.from_numpy(alpha_cumprods[grid])
         self.ddim_alpha_cumprods_prev = torch.from_numpy(np.asarray([alpha_cumprods[0]] + alpha_cumprods[grid[:-1]].tolist()))
         self.ddim_alpha_cumprods_next = torch.from_numpy(np.asarray(alpha_cumprods[grid[1:]].tolist() + [0.0]))
-
-        def interval_idx(n):
-            step = ddim_timesteps // n + int(ddim_timesteps % n > 0)
-            return torch.arange(step, ddim_timesteps, step) - 1
-
         if endpoints is None:
-            self.endpoints = torch.tensor([0] + self.ddim_timesteps[interval_idx(num_endpoints)].tolist())
+            self.endpoints = sampling.interval_endpoints(self.ddim_timesteps, num_endpoints, max_inverse_timestep_index)[0]
         else:
             self.endpoints = torch.tensor([int(e) for e in endpoints.split(',')])
             assert len(self.endpoints) == num_endpoints
         if inverse_endpoints is None:
-            idx = torch.tensor(interval_idx(num_inverse_endpoints).tolist() + [max_inverse_timestep_index])
-            self.inverse_endpoints = self.ddim_timesteps[idx]
+            self.inverse_endpoints = sampling.interval_endpoints(self.ddim_timesteps, num_inverse_endpoints, max_inverse_timestep_index)[1]
         else:
             self.inverse_endpoints = torch.tensor([int(e) for e in inverse_endpoints.split(',')])
             assert len(self.inverse_endpoints) == num_inverse_endpoints
@@ -132,30 +92,7 @@ class DDIMSolver:
         return a_next.sqrt() * pred_x0 + (1.0 - a_next).sqrt() * pred_noise
 
 
-def linear_schedule_old(t, guidance_scale, tau1, tau2):
-    u = t / 1000
-    if u <= tau1:
-        gamma = 1.0
-    elif u >= tau2:
-        gamma = 0.0
-    else:
-        gamma = (tau2 - u) / (tau2 - tau1)
-    return gamma * guidance_scale
-
-
 # --------------------------------------------------------------------------------------------- shared loop pieces
-_CONST_CACHE = {}
-
-
-def _cached(key, make):
-    v = _CONST_CACHE.get(key)
-    if v is None:
-        if len(_CONST_CACHE) > 256:
-            _CONST_CACHE.clear()
-        v = _CONST_CACHE[key] = make()
-    return v
-
-
 def _text_conditioning(pipe, prompt, compute_embeddings_fn, is_sdxl, device):
     if compute_embeddings_fn is not None:
         if is_sdxl:
@@ -170,56 +107,15 @@ def _text_conditioning(pipe, prompt, compute_embeddings_fn, is_sdxl, device):
     return prompt_embeds, enc
 
 
+_CONSTS = sampling.ConstCache()      # process-wide: its keys carry the schedule's value, pipelines come and go
+
+
 def _w_embedding(values, device, dtype):
-    key = ("w", tuple(float(v) for v in values), str(device), dtype)
-    return _cached(key, lambda: guidance_scale_embedding(torch.tensor([float(v) for v in values]), embedding_dim=512)
-                   .to(device=device, dtype=dtype))
-
-
-class _editing:
-    """`with unet.editing():` when `on` and the pipeline's UNet is the native one (anything else: no-op)."""
-
-    def __init__(self, pipe, on):
-        ctx = getattr(getattr(pipe, "unet", None), "editing", None)
-        self._ctx = ctx() if (on and ctx is not None) else None
-
-    def __enter__(self):
-        if self._ctx is not None:
-            self._ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self._ctx is not None:
-            self._ctx.__exit__(*exc)
+    return sampling.w_embedding(values, 512, device, dtype, _CONSTS)
 
 
 def _boundary_step(noise_pred, t, s, latents, prediction_type, alpha_schedule, sigma_schedule, out_dtype):
-    B = len(latents)
-    if latents.is_cuda and prediction_type == "epsilon":
-        from . import ops
-        ti, si = int(t), int(s)
-
-        def make():
-            a_s, s_s = (1.0, 0.0) if si == 0 else (float(alpha_schedule[si]), float(sigma_schedule[si]))
-            row = [float(alpha_schedule[ti]), float(sigma_schedule[ti]), a_s, s_s]
-            return torch.tensor([row] * B, dtype=torch.float32).to(latents.device)
-        coef = _cached(("coef", ti, si, B, str(latents.device), float(alpha_schedule[ti])), make)
-        return ops.x0_step(latents.contiguous(), noise_pred.contiguous(), coef, out_dtype=out_dtype)
-    dev = latents.device
-    return predicted_origin(noise_pred, torch.tensor([t] * B, device=dev), torch.tensor([s] * B, device=dev), latents,
-                            prediction_type, alpha_schedule.to(dev), sigma_schedule.to(dev)).to(out_dtype)
-
-
-def _expand_edit_latents(latents, batch_size, groups):
-    """Latents of an edit: one sample for all prompts (init_latent of the SD1.5 runner), one per prompt group, or one per prompt."""
-    n = latents.shape[0]
-    if n == batch_size:
-        return latents
-    if n == 1:
-        return latents.expand(batch_size, *latents.shape[1:]).contiguous()
-    if groups is not None and n == groups[0]:
-        return latents.repeat_interleave(groups[1], 0)
-    raise ValueError(f"sample_deterministic: {n} latents for {batch_size} prompts"
-                     + ("" if groups is None else f" in {groups[0]} groups of {groups[1]}"))
+    return sampling.boundary_step(noise_pred, t, s, latents, prediction_type, alpha_schedule, sigma_schedule, out_dtype, _CONSTS)
 
 
 # --------------------------------------------------------------------------------------------- forward (inversion)
@@ -250,15 +146,14 @@ def inverse_sample_deterministic(pipe, images, prompt, generator=None, num_scale
         boundary = timesteps[1:] + [999]
         timesteps, boundary_timesteps = torch.tensor(timesteps), torch.tensor(boundary)
 
-    alpha_schedule = torch.sqrt(pipe.scheduler.alphas_cumprod).cpu()
-    sigma_schedule = torch.sqrt(1 - pipe.scheduler.alphas_cumprod).cpu()
+    alpha_schedule, sigma_schedule = sampling.schedules(pipe.scheduler)
     kw = {} if resize_to is None else {'resize_to': resize_to}
     start_latents = pipe.prepare_latents(images, timesteps[0], batch_size, 1, prompt_embeds.dtype, device,
                                          generator=torch.Generator().manual_seed(seed), **kw)
     latents = start_latents.clone()
     w_embedding = None if guidance_scale is None else _w_embedding([guidance_scale] * batch_size, latents.device, latents.dtype)
     ptype = pipe.scheduler.config.prediction_type
-    with _editing(pipe, True):                       # forward steps amplify the per-evaluation error: accurate precision level (unet.py)
+    with sampling.editing(pipe, True):                    # forward steps amplify the per-evaluation error: accurate precision level (unet.py)
         for t, s in zip(timesteps.cpu(), boundary_timesteps.cpu()):
             noise_pred = pipe.unet(latents.to(prompt_embeds.dtype), t, encoder_hidden_states=prompt_embeds, return_dict=False,
                                    timestep_cond=w_embedding, added_cond_kwargs=encoded_text)[0]
@@ -289,9 +184,7 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
         raise ValueError(f"sample_deterministic: output_type must be one of {OUTPUT_TYPES}, got {output_type!r}")
     groups = None
     if controller is not None:
-        from . import p2p
-        from .generation import _prompt_groups
-        groups = _prompt_groups(prompt, controller)
+        groups = sampling.prompt_groups(prompt, controller)
         if groups is not None:
             prompt = [p for grp in prompt for p in grp]
         p2p.register_attention_control(pipe, controller)
@@ -321,7 +214,7 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
         ts = list(reversed(timesteps))                      # the caller's list is left untouched (deepcopy in the reference)
         timesteps, boundary_timesteps = torch.tensor(ts), torch.tensor(ts[1:] + [0])
 
-    alpha_schedule, sigma_schedule = torch.sqrt(ac).cpu(), torch.sqrt(1 - ac).cpu()
+    alpha_schedule, sigma_schedule = sampling.schedules(pipe.scheduler)
     if latents is None:
         latents = pipe.prepare_latents(batch_size, pipe.unet.config.in_channels, height, width, prompt_embeds.dtype, device,
                                        generator, None)
@@ -329,17 +222,13 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
     else:
         latents = latents.to(prompt_embeds.dtype)
         if controller is not None:
-            latents = _expand_edit_latents(latents, batch_size, groups)
+            latents = sampling.expand_edit_latents(latents, batch_size, groups)
     w_embedding = None if guidance_scale is None else _w_embedding([guidance_scale] * batch_size, latents.device, latents.dtype)
     ptype = pipe.scheduler.config.prediction_type
     # dynamic guidance = the reference's editing schedule, and a run with a controller is an edit: accurate precision level
-    edit_ctx = _editing(pipe, use_dynamic_guidance or controller is not None)
     # every sample of an SDXL batch is conditional: the controller acts on the whole batch (the executor's cond-only hook layout)
     hooked = controller is not None and hasattr(pipe.unet, "attn_cond_only")
-    edit_ctx.__enter__()
-    if hooked:
-        was_cond_only, pipe.unet.attn_cond_only = pipe.unet.attn_cond_only, True
-    try:
+    with sampling.editing(pipe, use_dynamic_guidance or controller is not None), sampling.cond_only(pipe.unet, hooked):
         for t, s in zip(timesteps.cpu(), boundary_timesteps.cpu()):
             if use_dynamic_guidance:
                 t_item = t if isinstance(t, int) else t.item()
@@ -355,10 +244,6 @@ def sample_deterministic(pipe, prompt, latents=None, generator=None, num_scales=
             latents = _boundary_step(noise_pred, t, s, latents, ptype, alpha_schedule, sigma_schedule, pipe.unet.dtype)
             if controller is not None:
                 latents = controller.step_callback(latents).to(pipe.unet.dtype)
-    finally:
-        if hooked:
-            pipe.unet.attn_cond_only = was_cond_only
-        edit_ctx.__exit__(None, None, None)
 
     vae = getattr(pipe, "vae", None)
     if vae is None:          # VAE decode is outside this path: hand the latents back

@@ -16,6 +16,8 @@ budget), which the samplers select for inversion loops, dynamic-guidance passes 
 generation runs at the 'fast' level (the error carry of round 4, one evaluation 0.70 - 0.85e-3), whose reverse loops contract the error
 (3e-4 after 4 steps).  For scale: an fp16 diffusers-style pipeline (the oracle graph in fp16 torch) sits at 2 - 2.6e-3 per evaluation.
 """
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -375,6 +377,32 @@ def test_boundary_step_round_trip_full_size():
             y = ops.x0_step(x, eps, fwd)
             back = ops.x0_step(y, eps, bwd)
             assert rel_l2(back, x) < 1e-5
+
+
+def test_both_samplers_boundary_step_equals_predicted_origin_in_fp32():
+    """The device branch of sampling.boundary_step through both callers (their cached [B, 4] coefficients, their output dtypes): the SD1.5
+    Generator hands back fp32, the SDXL wrapper the fp16 it is asked for, and both are predicted_origin evaluated in fp32 on the device -
+    bit for bit, the SDXL one after that value's rounding to fp16 - at a plain pair, at the hard boundary s = 0 and at a forward pair."""
+    E = _env()
+    G, X = E["generation"], E["generation_sdxl"]
+    sched = E["DDIMScheduler"].sd15()
+    solver = G.Generator(types.SimpleNamespace(tokenizer=None, scheduler=sched), 50, sched)      # the boundary step needs no UNet
+    alpha, sigma = G.sampling.schedules(sched)
+    gen = torch.Generator().manual_seed(7)
+    for dtype in (torch.float16, torch.float32):
+        x = torch.randn(2, 4, 8, 8, generator=gen).to(dtype).cuda()
+        eps = torch.randn(2, 4, 8, 8, generator=gen).to(dtype).cuda()
+        for t, s in ((999, 779), (259, 0), (19, 259)):
+            ts, ss = torch.tensor([t, t]).cuda(), torch.tensor([s, s]).cuda()
+            ref = G.predicted_origin(eps.float(), ts, ss, x.float(), "epsilon", alpha.cuda(), sigma.cuda())
+            assert ref.dtype == torch.float32
+            for _ in range(2):                                 # the second call takes its coefficients from the cache
+                a = solver._boundary_step(eps, torch.tensor(t), torch.tensor(s), x, alpha, sigma)
+                b = X._boundary_step(eps, torch.tensor(t), torch.tensor(s), x, "epsilon", alpha, sigma, torch.float16)
+                print(f"[boundary step {dtype} ({t}, {s})] max |sd15 - ref| = {float((a - ref).abs().max()):.3e}, "
+                      f"max |sdxl - fp16(ref)| = {float((b.float() - ref.half().float()).abs().max()):.3e}")
+                assert a.dtype == torch.float32 and torch.equal(a, ref)
+                assert b.dtype == torch.float16 and torch.equal(b, ref.half())
 
 
 def test_ddim_baseline_loops_match_oracle():
